@@ -21,6 +21,7 @@ for p in (REPO, os.path.join(REPO, "quadruped-springs_amd")):
         sys.path.insert(0, p)
 
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all; a larger output is cut to a fixed, seeded sample of environments
 
 
 def workload(name):
@@ -112,6 +113,24 @@ def cpu_baseline(cfg_kwargs, budget_s=14.0):
                         f"{one['envs']} envs x {one['env_steps'] // one['envs']} env-steps, {one['resets']} resets ({one['seconds']:.1f} s)"))
 
 
+def dump_outputs(directory, arrays, budget=DUMP_LIMIT_BYTES, prefix=""):
+    """Write the arrays of one step (leading axis = environment) as DIR/<prefix><name>.npy, float32 (float64 stays float64).  Over `budget`
+    bytes in all, the same rows of every array are kept: a sample of environments drawn with a fixed seed, whose indices go to
+    <prefix>sample_rows.npy -- two runs with the same arguments write the same files."""
+    import numpy as np
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        keep = max(1, int(budget // (total / n + 8)))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, prefix + k + ".npy"), np.ascontiguousarray(a))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -157,7 +176,14 @@ def parse_args(argv=None):
     ap.add_argument("--env-kw", nargs="*", action="extend", default=[], metavar="KEY=VALUE",
                     help="extra QuadrupedVecEnv keywords for experiments (python literals, anything else is taken as a string), "
                          "e.g. self_collision=False payload=soft env_randomizer_mode=MASS_RANDOMIZER")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (observation, reward, done, truncated; the gathered rows of "
+                         "config4_sharded) as DIR/<name>.npy, at most 64 MB in all; ranks above 0 prefix rank<r>_.  The inputs are seeded: two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -396,8 +422,9 @@ def main():
                     pass
             torch.cuda.synchronize()
 
-    def run(env_kw, with_exchange):
-        """Preparation + the timed region for one handle; returns the measurements of this rank."""
+    def run(env_kw, with_exchange, keep_outputs=False):
+        """Preparation + the timed region for one handle; returns the measurements of this rank (and, with keep_outputs, host copies of what
+        the last timed step returned)."""
         env = QuadrupedVecEnv(num_envs=n, device=local_rank, auto_reset=True, reset_lookahead=args.reset_lookahead, env_id_offset=n * rank,
                               seed=1234, **env_kw)   # Philox streams keyed by the global environment id: one job of n x world environments
         if args.no_settle_lanes and args.reset_lookahead:
@@ -421,8 +448,9 @@ def main():
 
             def sharded_step(_unused):
                 k = state["t"] % n_roll
-                shard.step(roll_act[k] if rank == 0 else None, out=roll_res[k if rank == 0 else 0], unpack=False)   # the rollout buffer keeps the fused rows
+                rows = shard.step(roll_act[k] if rank == 0 else None, out=roll_res[k if rank == 0 else 0], unpack=False)   # the rollout buffer keeps the fused rows
                 state["t"] += 1
+                return rows
 
             step_fn = sharded_step
         # Auto-reset: every environment takes its own next reset state (randomizer draws of (seed, environment, episode), spawn, 2500
@@ -462,13 +490,17 @@ def main():
         t0 = time.perf_counter()
         t_first = t0
         for i in range(args.steps):
-            step_fn(acts[i % n_act])
+            last = step_fn(acts[i % n_act])
             if debug and i == 0:
                 t_first = time.perf_counter()
         t_loop = time.perf_counter()
         env.enable_timing(2)                        # the closing event, in stream order behind the last launch; waited for after the region
         barrier()
         elapsed = time.perf_counter() - t0
+        outputs = None
+        if keep_outputs:    # (the step's result buffers are reused: copied before anything else runs on this handle)
+            names = ("rows",) if with_exchange else ("obs", "reward", "done", "truncated")
+            outputs = {k: x.detach().cpu().numpy() for k, x in zip(names, (last,) if with_exchange else last)}
         kernel_ms = env.last_step_kernel_ms()
         if debug:
             print(f"[debug] first call {1e6 * (t_first - t0):.0f} us, launching {1e6 * (t_loop - t0):.0f} us, until the barrier returned {1e6 * elapsed:.0f} us, kernel_ms x K {1e3 * kernel_ms * args.steps:.0f} us", file=sys.stderr)
@@ -486,7 +518,7 @@ def main():
             barrier()
             local_elapsed = time.perf_counter() - t1
         res = dict(elapsed=elapsed, kernel_ms=kernel_ms, local_elapsed=local_elapsed, delta={k: c1[k] - c0[k] for k in c0}, backlog=backlog,
-                   action_dim=d, obs_dim=env.obs_dim, settle_steps=env.cfg.settle_steps, lookahead=env.cfg.reset_lookahead)
+                   action_dim=d, obs_dim=env.obs_dim, settle_steps=env.cfg.settle_steps, lookahead=env.cfg.reset_lookahead, outputs=outputs)
         env.close()
         return res
 
@@ -496,7 +528,9 @@ def main():
     main_bc = kw.get("body_contacts", default_body_contacts(gloo))
     kw["body_contacts"] = main_bc
     other_bc = "auto" if main_bc is True else True
-    m = run(kw, sharded)
+    m = run(kw, sharded, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"], DUMP_LIMIT_BYTES // world, prefix="" if rank == 0 else f"rank{rank}_")
     m_info = None
     if not kw["info_fields"] and not args.no_info_line and not sharded:
         m_info = run(dict(kw, info_fields=True), False)

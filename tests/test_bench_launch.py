@@ -190,3 +190,49 @@ def test_counters_of_another_binary_are_not_reported(tmp_path):
 def test_headline_command_refuses_a_short_preroll():
     r = run(["--gpus", "1", "--steps", "1", "--warmup", "0", "--preroll", "100"])
     assert r.returncode != 0 and "two episode lengths" in r.stderr
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, one float .npy per array (rank 0 plain, rank r prefixed rank<r>_), through the
+    gloo test mode's stand-in; the inputs are seeded, so two runs with the same arguments write the same arrays."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "quadruped-springs_amd")]))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    got = []
+    for run_dir in (tmp_path / "a", tmp_path / "b"):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--standin", "bench_standin:StandInVecEnv",
+                              "--envs-per-gpu", "16", "--steps", "3", "--warmup", "1", "--preroll", "2", "--spread-steps", "125", "--no-info-line",
+                              "--no-body-contacts-line", "--dump-outputs", str(run_dir)], capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        files = sorted(p.name for p in run_dir.iterdir())
+        assert files == sorted(p + k + ".npy" for p in ("", "rank1_") for k in ("obs", "reward", "done", "truncated")), files
+        arrays = {f: np.load(run_dir / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["obs.npy"].ndim == 2 and arrays["obs.npy"].shape[0] == 16
+        assert arrays["reward.npy"].shape == arrays["done.npy"].shape == (16,)
+        got.append(arrays)
+    for f in got[0]:
+        np.testing.assert_array_equal(got[0][f], got[1][f], err_msg=f)
+
+
+def test_dump_outputs_samples_rows_above_the_budget(tmp_path):
+    """An output larger than the budget is cut to the same seeded sample of environments in every array; the indices are written too."""
+    sys.path.insert(0, REPO)
+    import bench
+    import numpy as np
+    n = 1000
+    obs = np.arange(n * 8, dtype=np.float32).reshape(n, 8)
+    done = (np.arange(n) % 3 == 0)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"obs": obs, "done": done}, budget=4096)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    total = sum(np.load(tmp_path / "a" / f).nbytes for f in ("obs.npy", "done.npy", "sample_rows.npy"))
+    assert total <= 4096
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "obs.npy"), obs[rows.astype(int)])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "done.npy"), done[rows.astype(int)].astype(np.float32))
+    for f in ("obs.npy", "done.npy", "sample_rows.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
