@@ -486,7 +486,9 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     // the full build: the wave that every launch waits for paid up to two steps' time.  Continuing inside the same function -- the full
     // build's substep loop behind the hot one -- was tried first: the values live across both loops put ~30 scratch instructions into the
     // hot loop, 112.1 -> 102.5 M env-steps/s.)
-    enum { RESUME_AT_BOUNDARY = 0x100 };
+    // (a bit no substep index reaches: qs_create refuses action_repeat and settle_steps at or above it.  Round 6 had 0x100, which a
+    // hand-over at substep k >= 256 of a long step set by itself -- misread as a boundary hand-over, resumed at k mod 256)
+    enum { RESUME_AT_BOUNDARY = 1 << 30 };
     enum { ST_CMD = 0, ST_KP = 12, ST_KD = 15, ST_W = 18, ST_CPGP = 22, ST_CPGR = 28, ST_CPGTH = 32 };
     static QS_FN void stash_state(float* rec, const typename S::State& s) {
         T::st(rec, R_POS, s.pos.x); T::st(rec, R_POS + 1, s.pos.y); T::st(rec, R_POS + 2, s.pos.z);

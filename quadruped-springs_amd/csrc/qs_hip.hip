@@ -707,6 +707,13 @@ int qs_create(const qs_config* cfg, int device, qs_handle** out) {
         QS_FAIL(-1, "the DEMO tasks compare the policy's action with a recorded one: they need an RL action space (not CPG, not raw commands)");
     if (cfg->task < 0 || cfg->task > QS_TASK_CONT_JUMPING_FORWARD_DEMO) QS_FAIL(-1, "unknown task id %d", cfg->task);
     if (cfg->friction_cone != 0 && cfg->friction_cone != 1) QS_FAIL(-1, "friction_cone must be 0 (pyramid) or 1 (implicit cone), got %d", cfg->friction_cone);
+    // the step hands a substep index over with a flag bit above it (Env::RESUME_AT_BOUNDARY); the settle lanes' schedule divides by both
+    if (cfg->action_repeat < 1 || cfg->action_repeat >= (int)E::RESUME_AT_BOUNDARY)
+        QS_FAIL(-1, "action_repeat must be between 1 and %d substeps per env step, got %d", (int)E::RESUME_AT_BOUNDARY - 1, cfg->action_repeat);
+    if (cfg->settle_steps < 0 || cfg->settle_steps >= (int)E::RESUME_AT_BOUNDARY)
+        QS_FAIL(-1, "settle_steps must be between 0 and %d substeps, got %d", (int)E::RESUME_AT_BOUNDARY - 1, cfg->settle_steps);
+    if (cfg->settle_steps == 0 && cfg->reset_lookahead > 0)
+        QS_FAIL(-1, "reset_lookahead > 0 settles reset states ahead of time in slices of the settle: it needs settle_steps > 0 (got 0; use reset_lookahead = 0)");
     if (cfg->reset_lookahead < 0 || cfg->reset_lookahead > 64) QS_FAIL(-1, "reset_lookahead must be between 0 (settle inside the step) and 64 reset states per environment, got %d", cfg->reset_lookahead);
     if (cfg->motor_control_mode == QS_MOTOR_TORQUE && cfg->rl_interface)  // gym_env.py:167-168
         QS_FAIL(-1, "the motor control mode TORQUE not implemented yet for RL Gym interface.");

@@ -8,17 +8,30 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _REPO = os.path.dirname(os.path.dirname(_HERE))
 _SO = os.path.join(_HERE, "libqs_emu.so")
+_SO_HOT = os.path.join(_HERE, "libqs_emu_hot.so")
 import glob
 # every header under csrc/ counts (round 4's hand-kept list lacked qs_rare.h: an edit of the many-rows solver left a stale emulation behind)
-_SRC = [os.path.join(_HERE, "qs_emu.cpp")] + sorted(glob.glob(os.path.join(_REPO, "quadruped-springs_amd", "csrc", "*.h"))) + \
-       [os.path.join(_REPO, "include", "qs_amd.h")]
+_HDR = sorted(glob.glob(os.path.join(_REPO, "quadruped-springs_amd", "csrc", "*.h"))) + \
+       [os.path.join(_REPO, "include", "qs_amd.h"), os.path.join(_HERE, "qs_emu.h")]
+_SRC = [os.path.join(_HERE, "qs_emu.cpp")] + _HDR
+
+
+def _compile(so, src):
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in [src] + _HDR):
+        tmp = "%s.%d.tmp" % (so, os.getpid())   # (renamed into place: a concurrent loader never sees half a library)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-ffp-contract=off",
+                               "-I" + os.path.join(_REPO, "include"), "-o", tmp, src])
+        os.replace(tmp, so)
+    return so
 
 
 def build():
-    if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRC):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-ffp-contract=off",
-                               "-I" + os.path.join(_REPO, "include"), "-o", _SO, _SRC[0]])
-    return _SO
+    return _compile(_SO, _SRC[0])
+
+
+def build_hot():
+    """the step kernels' common-path builds and their hand-over (qs_emu_hot.cpp): ~50 s of g++, so only on demand"""
+    return _compile(_SO_HOT, os.path.join(_HERE, "qs_emu_hot.cpp"))
 
 
 class Emu:
@@ -63,6 +76,36 @@ class Emu:
         trunc = np.zeros(self.n, np.uint8)
         self.lib.qse_step(self.h, self._p(a), self._p(obs), self._p(rew), self._p(done), self._p(trunc))
         return obs, rew, done.astype(bool), trunc.astype(bool)
+
+    def _hot(self):
+        if getattr(self, "_hot_lib", None) is None:
+            self._hot_lib = C.CDLL(build_hot())
+        return self._hot_lib
+
+    def step_hot(self, actions, variant):
+        """step() through the builds step kernel `variant` launches (1 = k_step, 2 = k_step_dense, as QS_STEP_VARIANT): the common-path
+        build, then the full build from the substep where it handed over.  resume: per environment -1 (not handed over) or the substep,
+        with resume_at_boundary() added for a hand-over between two substeps."""
+        a = np.ascontiguousarray(actions, np.float32).reshape(self.n, self.d)
+        obs = np.zeros((self.n, self.o), np.float32)
+        rew = np.zeros(self.n, np.float32)
+        done = np.zeros(self.n, np.uint8)
+        trunc = np.zeros(self.n, np.uint8)
+        resume = np.zeros(self.n, np.int32)
+        rc = self._hot().qse_step_hot(self.h, self._p(a), self._p(obs), self._p(rew), self._p(done), self._p(trunc), int(variant), self._p(resume))
+        assert rc == 0, rc
+        return obs, rew, done.astype(bool), trunc.astype(bool), resume
+
+    def resume_at_boundary(self):
+        return int(self._hot().qse_resume_at_boundary())
+
+    def settle_slice(self, settle_n, spawn=False, variant=0):
+        """one slice of a reset's settle as a settle lane runs it: `spawn` first draws the next episode's parameters and spawn state;
+        variant 0 = the full build, 1 / 2 = the step kernels' builds with their hand-over.  Returns resume as step_hot does."""
+        resume = np.zeros(self.n, np.int32)
+        rc = self._hot().qse_settle_slice(self.h, int(settle_n), int(bool(spawn)), int(variant), self._p(resume))
+        assert rc == 0, rc
+        return resume
 
     def set_trace(self, env):
         self._trace = np.zeros((self.cfg.action_repeat, 70), np.float32)

@@ -1,20 +1,7 @@
 // qs_emu.cpp -- TEST-ONLY host emulation of the quad-per-environment kernels.
 // Instantiates the kernel arithmetic of quadruped-springs_amd/csrc/qs_env.h with the 4-wide LaneEmu type so that the
 // CPU test-suite (no GPU in the build container) can compare it with the oracle.  Never linked into the product.
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
-#include "../../quadruped-springs_amd/csrc/qs_env.h"
-
-using E = qs::Env<LaneEmu>;            // friction pyramid
-using EC = qs::Env<LaneEmu, true>;     // implicit cone (cfg.friction_cone): the kernels are built for both, so is this harness
-
-struct Emu {
-    qs_config cfg;
-    std::vector<float> rec, obs, term_obs;
-    float* trace = nullptr; int trace_env = -1;
-    std::vector<float> demo; int demo_len = 0;
-};
+#include "qs_emu.h"
 
 static void init_record(const qs_config& cfg, float* r, int env) {
     memset(r, 0, QS_REC * sizeof(float));
@@ -106,13 +93,7 @@ int qse_step(void* h, const float* actions, float* obs, float* rew, uint8_t* don
         float rw, dn, tc;
         if (e->cfg.friction_cone) { EC::StepOut r = EC::step(e->cfg, rec, actions + (size_t)i * d, ob, (uint32_t)(i + e->cfg.env_id_offset), 0, tr, tr != nullptr, e->demo.data(), e->demo_len); rw = r.reward.v[0]; dn = r.done.v[0]; tc = r.trunc.v[0]; }
         else { E::StepOut r = E::step(e->cfg, rec, actions + (size_t)i * d, ob, (uint32_t)(i + e->cfg.env_id_offset), 0, tr, tr != nullptr, e->demo.data(), e->demo_len); rw = r.reward.v[0]; dn = r.done.v[0]; tc = r.trunc.v[0]; }
-        rew[i] = rw; done[i] = dn > 0.5f; trunc[i] = tc > 0.5f;
-        if (done[i] && e->cfg.auto_reset) {
-            memcpy(&e->term_obs[(size_t)i * QS_MAX_OBS], ob, QS_MAX_OBS * sizeof(float));
-            if (e->cfg.friction_cone) EC::reset(e->cfg, rec, ob, (uint32_t)(i + e->cfg.env_id_offset), true);
-            else E::reset(e->cfg, rec, ob, (uint32_t)(i + e->cfg.env_id_offset), true);
-        }
-        memcpy(obs + (size_t)i * e->cfg.obs_dim, ob, e->cfg.obs_dim * sizeof(float));
+        finish_env_step(e, i, rw, dn, tc, obs, rew, done, trunc);
     }
     return 0;
 }

@@ -101,6 +101,32 @@ def test_no_gpu_means_loud_failure():
     assert b"no HIP device" in lib.load().qs_last_error() or b"failed" in lib.load().qs_last_error()
 
 
+@pytest.mark.parametrize("field,value,needle", [
+    ("action_repeat", 0, b"action_repeat must be between 1 and"),
+    ("action_repeat", -3, b"action_repeat must be between 1 and"),
+    ("action_repeat", 1 << 30, b"action_repeat must be between 1 and"),
+    ("settle_steps", -1, b"settle_steps must be between 0 and"),
+    ("settle_steps", 1 << 30, b"settle_steps must be between 0 and"),
+    ("settle_steps", 0, b"needs settle_steps > 0"),
+])
+def test_create_refuses_substep_counts_the_step_cannot_run(field, value, needle):
+    """qs_create validates the config before it looks for a device: a step's substep index travels with a flag bit above it through the
+    hand-over to the full build (Env::RESUME_AT_BOUNDARY = 1 << 30), and the settle lanes' schedule divides by action_repeat and by the
+    slices of a settle -- counts outside what that allows are refused with their own message, on any machine."""
+    from qs_amd import lib
+    cfg, _ = build_config(n_envs=2)
+    cfg.reset_lookahead = 16
+    setattr(cfg, field, value)
+    h = C.c_void_p()
+    assert lib.load().qs_create(C.byref(cfg), 0, C.byref(h)) != 0
+    assert needle in lib.load().qs_last_error(), lib.load().qs_last_error()
+    cfg, _ = build_config(n_envs=2)       # without look-ahead resets a reset settles inside the step: settle_steps = 0 is fine there
+    cfg.settle_steps, cfg.reset_lookahead = 0, 0
+    assert lib.load().qs_create(C.byref(cfg), 0, C.byref(h)) == 0 or b"settle_steps" not in lib.load().qs_last_error()
+    if h.value:
+        lib.load().qs_destroy(h)
+
+
 def test_registries_and_errors_mirror_the_reference():
     cfg, meta = build_config(task_env="JUMPING_IN_PLACE", observation_space_mode="PPO_BASIC", enable_springs=True)
     assert cfg.action_dim == 6 and cfg.obs_dim == 28 and cfg.solver_iters == 30 and cfg.settle_steps == 2500
