@@ -62,9 +62,8 @@ def hipcc():
     raise RuntimeError("hipcc not found (set HIPCC)")
 
 
-def build(force=False, verbose=False):
-    if not force and not needs_build():
-        return OUT
+def hipcc_flags(with_form=True):
+    """hipcc's options for gfx950 code, without sources and output: the product library's (build()) and the test-only probes' (tests/hip/)."""
     # -fno-slp-vectorize: packed fp32 (v_pk_*) costs more moves than it saves here.  iterative-ilp: with one wave per SIMD
     # there is no other wave to hide a dependent instruction's latency, so the scheduler should chase ILP, not occupancy
     # (measured +6.5 % env-steps/s over the default strategy, same instructions, same results).
@@ -91,13 +90,19 @@ def build(force=False, verbose=False):
     # build that ran <0, 4> and <0, 6> side by side on the same rows (-DQS_DBG_CORE4, tools/diag/core4_differential.py) found them equal bit
     # for bit: the damage is in the spill code around the solve, not in it.  Without the option the library is as fast (70.5 / 111.5 M
     # against 70.4 / 111.0 M, gpurun_out/ab_tmp2) and every parity gate is green again.
+    return ["--offload-arch=" + os.environ.get("QS_OFFLOAD_ARCH", "gfx950"), "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-fno-slp-vectorize",
+            "-ffinite-math-only", "-fno-signed-zeros", "-fno-trapping-math", "-ffp-contract=on",
+            "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] + (["-mllvm", "-amdgpu-mfma-vgpr-form"] if with_form else []) + \
+        os.environ.get("QS_HIPCC_EXTRA", "").split()
+
+
+def build(force=False, verbose=False):
+    if not force and not needs_build():
+        return OUT
     vgpr_form = os.environ.get("QS_MFMA_VGPR_FORM", "1") != "0"
 
     def command(with_form):
-        c = [hipcc(), "--offload-arch=" + os.environ.get("QS_OFFLOAD_ARCH", "gfx950"), "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-fno-slp-vectorize",
-             "-ffinite-math-only", "-fno-signed-zeros", "-fno-trapping-math", "-ffp-contract=on",
-             "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] + (["-mllvm", "-amdgpu-mfma-vgpr-form"] if with_form else []) + \
-            os.environ.get("QS_HIPCC_EXTRA", "").split() + ['-DQS_SOURCE_SHA="' + source_fingerprint() + '"', "-I" + os.path.join(REPO, "include"), "-o", os.environ.get("QS_BUILD_OUT") or OUT, SRC, SRC_NORM]
+        c = [hipcc()] + hipcc_flags(with_form) + ['-DQS_SOURCE_SHA="' + source_fingerprint() + '"', "-I" + os.path.join(REPO, "include"), "-o", os.environ.get("QS_BUILD_OUT") or OUT, SRC, SRC_NORM]
         if verbose:
             c.insert(1, "-Rpass-analysis=kernel-resource-usage")
             print(" ".join(c))

@@ -175,6 +175,9 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
     // xr: the twelve rows of this lane's leg; pay: the block's rows (replicated over the quad) or nullptr; mine: this lane's environment has
     // rare rows; warm: the foot's warm-start impulse (already x cfg.warmstart x act); scr: RarePos::SCRATCH_FLOATS floats of LDS shared by
     // the wave.  Results (for the lanes with `mine`, zero elsewhere): lam12 = the impulses of the lane's twelve rows, plam = the payload rows'.
+    // CORE: which core<> takes the solve -- 0 picks by the shape (the product), 1 / 2 / 3 force <0, 4> / <0, 6> / <NA, NB> (tests/hip/rare_probe.hip;
+    // <0, 4> and <0, 6> only hold solves without region A and with at most 4 / 6 contact points).
+    template <int CORE = 0>
     static QS_DEV void solve(const qs_config& cfg, float mu, const Row* xr, const PayRows* pay, bool mine, float warm, float* scr, float* lam12, float* plam) {
         using P = RarePos;
         constexpr int A0 = 0, B0 = P::NRM0, C0 = P::FRI0, NA = P::NRM0, NB = P::FRI0 - P::NRM0;
@@ -293,6 +296,10 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
             // every one of the benchmark's -- takes an instantiation with 18 (12: four contact points) coefficient registers instead of 72: the
             // sweep loop of the large one re-read ~ 30 coefficients from AGPRs and SGPR-spill lanes at the head of every sweep
             int n_sweeps = 0;
+            if constexpr (CORE == 1) core<0, 4>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if constexpr (CORE == 2) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if constexpr (CORE == 3) core<NA, NB>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else {
 #ifdef QS_DBG_CORE4   // diagnostic: both small instantiations on the same rows, bitwise mismatches into the self-narrow counter (tools/diag/core4_differential.py)
             if (mA == 0 && mB <= 4) {
                 float lam6 = lam; int ns6 = 0;
@@ -309,6 +316,7 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
             else if (mA == 0 && mB <= 6) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
             else core<NA, NB>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
 #endif
+            }
             QS_PHASE_G(43)
 #if defined(QS_PROFILE_PHASES) && defined(__HIP_DEVICE_COMPILE__)
             if (threadIdx.x == 0) {   // all workgroups: solves, sweeps, live rows, live contact points (normals)
@@ -346,6 +354,11 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ------------------------------------------------------------------ the same solve for the 4-wide host emulation (tests only): one
 // environment, plain loops over its rows in the same order
+#ifndef QS_RARE_CAPTURE
+// QS_RARE_CAPTURE(cfg, mu, xr, pay, mine, warm): called with the inputs of every solve; a test translation unit of the emulation defines it
+// (tests/emu/qs_emu.cpp: the row sets of tests/test_rare_solver.py)
+#define QS_RARE_CAPTURE(cfg, mu, xr, pay, mine, warm)
+#endif
 template <bool CONE> struct RareSolver<LaneEmu, CONE> {
     using Ty = SimTypes<LaneEmu>;
     using Row = typename Ty::Row;
@@ -355,6 +368,7 @@ template <bool CONE> struct RareSolver<LaneEmu, CONE> {
         for (int r = 0; r < 12; r++) lam12[r] = V4(0.0f);
         for (int k = 0; k < 6; k++) plam[k] = V4(0.0f);
         if (!mine.v[0]) return;
+        QS_RARE_CAPTURE(cfg, mu, xr, pay, mine, warm);
         float w[P::N][6], a[P::N][3], b[P::N][3], rhs[P::N], dinv[P::N], diag[P::N], lam[P::N], res[P::N];
         bool live[P::N];
         for (int p = 0; p < P::N; p++) {

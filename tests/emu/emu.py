@@ -154,3 +154,41 @@ class Emu:
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(values, np.int32), (self.n,)))
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         self.lib.qse_set_demo_counter(self.h, None if m is None else self._p(m), self._p(v))
+
+
+def rare_solve(cfg, rows, env, warm, pay=None):
+    """the emulation twin of the many-rows solve (RareSolver<LaneEmu, cfg.friction_cone>, qs_rare.h) on row sets in the layout of
+    tests/hip/probe.py: rows [n, 4, 12, 16], env [n, 2] (mu, mine), warm [n, 4], pay [n, 59] or None -> lam12 [n, 4, 12], plam [n, 6]"""
+    lib = C.CDLL(build())
+    rows, env, warm = (np.ascontiguousarray(x, np.float32) for x in (rows, env, warm))
+    n = rows.shape[0]
+    assert rows.shape == (n, 4, 12, 16) and env.shape == (n, 2) and warm.shape == (n, 4)
+    pay = None if pay is None else np.ascontiguousarray(pay, np.float32).reshape(n, 59)
+    lam12, plam = np.zeros((n, 4, 12), np.float32), np.zeros((n, 6), np.float32)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    rc = lib.qse_rare_solve(C.byref(cfg), n, p(rows), p(env), p(warm), p(pay), p(lam12), p(plam))
+    assert rc == 0, rc
+    return lam12, plam
+
+
+class RareCapture:
+    """`with RareCapture(max_sets) as cap:` records the inputs of the emulation's many-rows solves (qse_rare_capture) while steps run;
+    afterwards cap.rows / env / warm / pay (None where a solve had no payload rows) as rare_solve() takes them"""
+
+    def __init__(self, max_sets=4096):
+        self.max_sets = max_sets
+
+    def __enter__(self):
+        self.lib = C.CDLL(build())
+        self.rec = self.lib.qse_rare_capture(int(self.max_sets))
+        return self
+
+    def __exit__(self, *exc):
+        n = self.lib.qse_rare_captured(None)
+        buf = np.zeros((n, self.rec), np.float32)
+        self.lib.qse_rare_captured(buf.ctypes.data_as(C.c_void_p))
+        self.lib.qse_rare_capture(0)
+        self.rows = buf[:, :768].reshape(n, 4, 12, 16)
+        self.env, self.warm = buf[:, 768:770], buf[:, 770:774]
+        self.pay, self.has_pay = buf[:, 774:833], buf[:, 833] > 0.5
+        return False

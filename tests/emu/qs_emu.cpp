@@ -1,7 +1,77 @@
 // qs_emu.cpp -- TEST-ONLY host emulation of the quad-per-environment kernels.
 // Instantiates the kernel arithmetic of quadruped-springs_amd/csrc/qs_env.h with the 4-wide LaneEmu type so that the
 // CPU test-suite (no GPU in the build container) can compare it with the oracle.  Never linked into the product.
+#include <mutex>
+// the many-rows solve's inputs, captured while steps run (qse_rare_capture; tests/test_rare_solver.py): qs_rare.h's emulation twin calls
+// QS_RARE_CAPTURE with them, a no-op unless defined before the kernel headers
+template <class V, class R, class P> static void rare_capture(const V& mu, const R* xr, const P* pay, const V& warm);
+#define QS_RARE_CAPTURE(cfg, mu, xr, pay, mine, warm) rare_capture(mu, xr, pay, warm)
 #include "qs_emu.h"
+
+// One environment's row set, laid out as tests/hip/rare_probe.hip takes it: rows [4 legs][12][16] (a Row's fields in struct order), mu,
+// mine, warm [4], the payload rows [59] (w 36, rhs 6, dinv 6, diag 6, rB 3, mI, act), then 1 if the solve had payload rows at all.
+enum { RARE_ROW_F = 16, RARE_ROWS = 4 * 12 * RARE_ROW_F, RARE_ENV = RARE_ROWS, RARE_WARM = RARE_ENV + 2, RARE_PAY = RARE_WARM + 4, RARE_PAY_F = 59,
+       RARE_HAS_PAY = RARE_PAY + RARE_PAY_F, RARE_REC = RARE_HAS_PAY + 1 };
+static std::mutex g_cap_mu;
+static std::vector<float> g_cap;
+static size_t g_cap_max = 0;
+
+template <class V, class R, class P> static void rare_capture(const V& mu, const R* xr, const P* pay, const V& warm) {
+    std::lock_guard<std::mutex> lk(g_cap_mu);
+    if (g_cap.size() >= g_cap_max * RARE_REC) return;
+    float r[RARE_REC] = {};
+    for (int L = 0; L < 4; L++)
+        for (int k = 0; k < 12; k++) {
+            float* q = r + (12 * L + k) * RARE_ROW_F;
+            for (int i = 0; i < 3; i++) { q[i] = xr[k].jq[i].v[L]; q[3 + i] = xr[k].u[i].v[L]; }
+            for (int i = 0; i < 6; i++) q[6 + i] = xr[k].w[i].v[L];
+            q[12] = xr[k].rhs.v[L]; q[13] = xr[k].dinv.v[L]; q[14] = xr[k].act.v[L]; q[15] = xr[k].diag.v[L];
+        }
+    r[RARE_ENV] = mu.v[0]; r[RARE_ENV + 1] = 1.0f;
+    for (int L = 0; L < 4; L++) r[RARE_WARM + L] = warm.v[L];
+    if (pay) {
+        float* q = r + RARE_PAY;
+        for (int k = 0; k < 6; k++) {
+            for (int i = 0; i < 6; i++) q[6 * k + i] = pay->w[k][i].v[0];
+            q[36 + k] = pay->rhs[k].v[0]; q[42 + k] = pay->dinv[k].v[0]; q[48 + k] = pay->diag[k].v[0];
+        }
+        q[54] = pay->rB.x.v[0]; q[55] = pay->rB.y.v[0]; q[56] = pay->rB.z.v[0]; q[57] = pay->mI.v[0]; q[58] = pay->act.v[0];
+        r[RARE_HAS_PAY] = 1.0f;
+    }
+    g_cap.insert(g_cap.end(), r, r + RARE_REC);
+}
+
+template <bool CONE> static void rare_solve_impl(const qs_config& cfg, int n_envs, const float* rows, const float* env, const float* warm, const float* pay,
+                                                 float* lam12, float* plam) {
+    using Ty = qs::SimTypes<LaneEmu>;
+    for (int e = 0; e < n_envs; e++) {
+        typename Ty::Row xr[12];
+        for (int k = 0; k < 12; k++)
+            for (int L = 0; L < 4; L++) {
+                const float* q = rows + ((size_t)(4 * e + L) * 12 + k) * RARE_ROW_F;
+                for (int i = 0; i < 3; i++) { xr[k].jq[i].v[L] = q[i]; xr[k].u[i].v[L] = q[3 + i]; }
+                for (int i = 0; i < 6; i++) xr[k].w[i].v[L] = q[6 + i];
+                xr[k].rhs.v[L] = q[12]; xr[k].dinv.v[L] = q[13]; xr[k].act.v[L] = q[14]; xr[k].diag.v[L] = q[15];
+            }
+        typename Ty::PayRows pr;
+        if (pay) {
+            const float* q = pay + (size_t)e * RARE_PAY_F;
+            for (int k = 0; k < 6; k++) {
+                for (int i = 0; i < 6; i++) pr.w[k][i] = V4(q[6 * k + i]);
+                pr.rhs[k] = V4(q[36 + k]); pr.dinv[k] = V4(q[42 + k]); pr.diag[k] = V4(q[48 + k]);
+            }
+            pr.rB = qs::mk3<V4>(V4(q[54]), V4(q[55]), V4(q[56])); pr.mI = V4(q[57]); pr.act = V4(q[58]);
+        }
+        const bool mine = env[2 * e + 1] > 0.5f;
+        const M4 m = {{mine, mine, mine, mine}};
+        const float* wp = warm + 4 * (size_t)e;
+        V4 lam[12], pl[6];
+        qs::RareSolver<LaneEmu, CONE>::solve(cfg, V4(env[2 * e]), xr, pay ? &pr : nullptr, m, V4(wp[0], wp[1], wp[2], wp[3]), nullptr, lam, pl);
+        for (int L = 0; L < 4; L++)
+            for (int k = 0; k < 12; k++) lam12[(size_t)(4 * e + L) * 12 + k] = lam[k].v[L];
+        for (int k = 0; k < 6; k++) plam[(size_t)e * 6 + k] = pl[k].v[0];
+    }
+}
 
 static void init_record(const qs_config& cfg, float* r, int env) {
     memset(r, 0, QS_REC * sizeof(float));
@@ -136,6 +206,21 @@ int qse_obb_overlap(const float* ca, const float* Ra, const float* ha, const flo
     M4 m = S::obb_overlap(qs::mk3<V4>(V4(ca[0]), V4(ca[1]), V4(ca[2])), col(Ra, 0), col(Ra, 1), col(Ra, 2), HA,
                           qs::mk3<V4>(V4(cb[0]), V4(cb[1]), V4(cb[2])), col(Rb, 0), col(Rb, 1), col(Rb, 2), HB);
     return m.v[0] ? 1 : 0;
+}
+// the emulation twin of the many-rows solve (RareSolver<LaneEmu, cfg.friction_cone>) on row sets laid out as tests/hip/rare_probe.hip's
+// qsp_rare_solve takes them: rows [n_envs x 4][12][16], env [n_envs][2] (mu, mine), warm [n_envs x 4], pay [n_envs][59] or null
+int qse_rare_solve(const qs_config* cfg, int n_envs, const float* rows, const float* env, const float* warm, const float* pay, float* lam12, float* plam) {
+    if (cfg->friction_cone) rare_solve_impl<true>(*cfg, n_envs, rows, env, warm, pay, lam12, plam);
+    else rare_solve_impl<false>(*cfg, n_envs, rows, env, warm, pay, lam12, plam);
+    return 0;
+}
+// capture the inputs of the next `max_sets` many-rows solves (0: stop); qse_rare_captured copies them out (RARE_REC floats each) and clears
+int qse_rare_capture(int max_sets) { std::lock_guard<std::mutex> lk(g_cap_mu); g_cap.clear(); g_cap_max = (size_t)(max_sets > 0 ? max_sets : 0); return RARE_REC; }
+int qse_rare_captured(float* out) {
+    std::lock_guard<std::mutex> lk(g_cap_mu);
+    const int n = (int)(g_cap.size() / RARE_REC);
+    if (out) { memcpy(out, g_cap.data(), g_cap.size() * sizeof(float)); g_cap.clear(); g_cap_max = 0; }
+    return n;
 }
 // one physics substep of env `i` under given joint torques (KATs on the kernel arithmetic)
 int qse_phys_step(void* h, int i, const float* tau12) {
