@@ -42,8 +42,9 @@ template <class T, bool CONE> struct RareSolver;
 // code stays structured (a goto per row, or a switch that falls through the rows, comes out of LLVM's CFG structurizer as flag variables
 // and four branches per row: measured 1.2 k cycles per sweep of ten rows)
 #define QS_NEST12(count, M) if (0 < (count)) { M(0) if (1 < (count)) { M(1) if (2 < (count)) { M(2) if (3 < (count)) { M(3) if (4 < (count)) { M(4) if (5 < (count)) { M(5) if (6 < (count)) { M(6) if (7 < (count)) { M(7) if (8 < (count)) { M(8) if (9 < (count)) { M(9) if (10 < (count)) { M(10) if (11 < (count)) { M(11) }}}}}}}}}}}}
-#define QS_NEST4(count, M) if (0 < (count)) { M(0) if (1 < (count)) { M(1) if (2 < (count)) { M(2) if (3 < (count)) { M(3) }}}}
-#define QS_NEST6(count, M) if (0 < (count)) { M(0) if (1 < (count)) { M(1) if (2 < (count)) { M(2) if (3 < (count)) { M(3) if (4 < (count)) { M(4) if (5 < (count)) { M(5) }}}}}}
+// M(0) .. M(N - 1), all of them: the small cores sweep their instantiation's N contact points whatever the count, the rows that do not
+// exist padded to exact zeros (core<>, below) -- one basic block per sweep instead of a branch per row
+#define QS_ALL(N, M) _Pragma("unroll") for (int j_ = 0; j_ < (N); j_++) { M(j_) }
 #define QS_NEST18(count, M) if (0 < (count)) { M(0) if (1 < (count)) { M(1) if (2 < (count)) { M(2) if (3 < (count)) { M(3) if (4 < (count)) { M(4) if (5 < (count)) { M(5) if (6 < (count)) { M(6) if (7 < (count)) { M(7) if (8 < (count)) { M(8) if (9 < (count)) { M(9) if (10 < (count)) { M(10) if (11 < (count)) { M(11) if (12 < (count)) { M(12) if (13 < (count)) { M(13) if (14 < (count)) { M(14) if (15 < (count)) { M(15) if (16 < (count)) { M(16) if (17 < (count)) { M(17) }}}}}}}}}}}}}}}}}}
 
 #if defined(__HIPCC__)
@@ -61,16 +62,20 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
     static QS_DEV int rli(int x, int lane) { return __builtin_amdgcn_readlane(x, lane); }
 
     // Delassus column, candidates and sweeps of one environment's solve (the lanes hold their rows: w, a, b, rhs, dinv, diag, lam, lo, hi, grp).
-    // NAX / NBX: how many rows of region A / contact points the coefficient arrays hold -- <18, 12> takes everything, <0, 6> what the benchmark's
-    // falling robots need (no joint at its stop, six contact points at most) with a quarter of the registers, <0, 4> the four-point solves among
-    // them with a sixth (round 5: 66.2 -> 68.1 -> 70.3 M on the benchmark; a finer ladder -- <0, 2>, <0, 3> -- added nothing).
+    // NAX / NBX: how many rows of region A / contact points the coefficient arrays hold -- <18, 12> takes everything, <0, 1> .. <0, 6> what the
+    // benchmark's falling robots need (no joint at its stop, six contact points at most) with a quarter of the registers or fewer (round 5:
+    // 66.2 -> 68.1 -> 70.3 M on the benchmark with <0, 6> and <0, 4>, whose sweeps still branched per row; a finer ladder added nothing then).
+    // The small ones (NAX = 0) are straight-line code: all NBX contact points in every sweep, no branch per row.  A count below NBX (solve<1>
+    // and <2> force <0, 4> / <0, 6>; <0, 1> takes mB = 0) is padded with lanes that hold no row: solve() zeroes their row data, so their
+    // columns, candidates, impulses and the changes they pass on are exact zeros, and the real rows see the same arithmetic in the same order.
     template <int NAX, int NBX>
     static QS_DEV void core(const qs_config& cfg, const float (&w)[6], const float (&a)[3], const float (&b)[3], float rhs, float dinv, float diag, float& lam,
                             float lo, float hi, int grp, int mA, int mB, float mu_e, bool track, float thr, int& n_sweeps) {
         using P = RarePos;
         constexpr int A0 = 0, B0 = P::NRM0, C0 = P::FRI0, IB = NAX, IC = NAX + NBX;
+        static_assert(NBX > 6 || NAX == 0, "the padded cores hold contact points only");
         const int lane = (int)threadIdx.x;
-            // ---- this lane's column of the Delassus matrix, x (-1 / A_pp): Ap[J] = what a unit impulse of the row in lane J does to this
+        // ---- this lane's column of the Delassus matrix, x (-1 / A_pp): Ap[J] = what a unit impulse of the row in lane J does to this
         // lane's candidate.  The row data of lane J come over by v_readlane (SGPRs); the self entry is zero.
         float Ap[NAX + 3 * NBX], ApR[NAX > 0 ? NAX : 1];
         {
@@ -97,7 +102,7 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
 #define QS_W_COL_R(j) QS_W_COL(ApR[(j)], mA - 1 - (j))
 #define QS_W_COL_B(j) QS_W_COL(Ap[IB + (j)], B0 + (j)) QS_W_COL(Ap[IC + 2 * (j)], C0 + 2 * (j)) QS_W_COL(Ap[IC + 2 * (j) + 1], C0 + 2 * (j) + 1)
             if constexpr (NAX > 0) { QS_NEST18(mA, QS_W_COL_A) QS_NEST18(mA, QS_W_COL_R) }
-            if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_COL_B) } else if constexpr (NBX > 4) { QS_NEST6(mB, QS_W_COL_B) } else { QS_NEST4(mB, QS_W_COL_B) }
+            if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_COL_B) } else { QS_ALL(NBX, QS_W_COL_B) }
 #undef QS_W_COL_A
 #undef QS_W_COL_R
 #undef QS_W_COL_B
@@ -107,7 +112,7 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
         // ---- candidates: rhs - dinv sum_{j != p} A_pj lambda_j; the warm start of the feet's normal rows is in already
         float res = rhs;
 #define QS_W_WARM(j) res = fmaf(Ap[IB + (j)], rl(lam, B0 + (j)), res);
-        if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_WARM) } else if constexpr (NBX > 4) { QS_NEST6(mB, QS_W_WARM) } else { QS_NEST4(mB, QS_W_WARM) }
+        if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_WARM) } else { QS_ALL(NBX, QS_W_WARM) }
 #undef QS_W_WARM
         // one row: every lane clamps its own candidate, the owner's change goes round
 #define QS_W_ROW(COEF, J)                                                                                              \
@@ -123,7 +128,7 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
         // bounded by mu x the normal impulse and left alone while that is not positive (Bullet's rule)
 #define QS_W_FRICTION(KK)                                                                                              \
     {                                                                                                                  \
-        constexpr int FP = C0 + 2 * (KK);                                                                              \
+        const int FP = C0 + 2 * (KK);                                                                                 \
         if (CONE) {                                                                                                    \
         const float lim_ = rl(lam * mu_e, B0 + (KK));          /* (every lane's product; the normal's counts) */   \
         const float ca_ = rl(res, FP), cb_ = rl(res, FP + 1);                                                      \
@@ -160,13 +165,15 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
                 if (it & 1) { QS_NEST18(mA, QS_W_FWD_A) }   // limit rows, then the payload rows, forwards; on even sweeps the same backwards
                 else { QS_NEST18(mA, QS_W_BWD_A) }
             }
-            if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_FWD_B) QS_NEST12(mB, QS_W_FWD_C) } else if constexpr (NBX > 4) { QS_NEST6(mB, QS_W_FWD_B) QS_NEST6(mB, QS_W_FWD_C) } else { QS_NEST4(mB, QS_W_FWD_B) QS_NEST4(mB, QS_W_FWD_C) }
+            if constexpr (NBX > 6) { QS_NEST12(mB, QS_W_FWD_B) QS_NEST12(mB, QS_W_FWD_C) } else { QS_ALL(NBX, QS_W_FWD_B) QS_ALL(NBX, QS_W_FWD_C) }
 #undef QS_W_FWD_A
 #undef QS_W_BWD_A
 #undef QS_W_FWD_B
 #undef QS_W_FWD_C
-            // PyBullet's solverResidualThreshold: every row moved once in this sweep, by lam - lam_in
-            if (track && !__any(fabsf((lam - lam_in) * diag) > thr)) break;
+            // PyBullet's solverResidualThreshold: every row moved once in this sweep, by lam - lam_in.  (The vote is taken whether or not
+            // it counts: under `track &&` it sat in a block of its own, three more branches at the end of every sweep.)
+            const bool moving = __any(fabsf((lam - lam_in) * diag) > thr);
+            if (track && !moving) break;
         }
 #undef QS_W_FRICTION
 #undef QS_W_ROW
@@ -289,12 +296,21 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
                 rhs = r3.y; dinv = r3.z; diag = r3.w;
                 const bool payrow = inA && lane >= A0 + mLim;
                 lo = payrow ? -bound : 0.0f; hi = payrow ? bound : big;
-                if (!alive) { grp = -1; rhs = 0.0f; diag = 0.0f; lam = 0.0f; }
+                // (a lane without a row -- padding of the small cores among them -- reads the dummy record, which may hold anything, NaN too:
+                // all-zero row data make its Delassus column, its candidate and thus its impulse and every change it passes on exactly 0)
+                if (!alive) {
+                    grp = -1; rhs = 0.0f; diag = 0.0f; lam = 0.0f; dinv = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 6; i++) w[i] = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 3; i++) { a[i] = 0.0f; b[i] = 0.0f; }
+                }
             }
             QS_PHASE_G(41)
             // ---- Delassus column, candidates, sweeps (core<>, above).  A solve without limit / payload rows and with six contact points at most --
-            // every one of the benchmark's -- takes an instantiation with 18 (12: four contact points) coefficient registers instead of 72: the
-            // sweep loop of the large one re-read ~ 30 coefficients from AGPRs and SGPR-spill lanes at the head of every sweep
+            // every one of the benchmark's -- takes the straight-line instantiation of ITS count, 3 x mB coefficient registers instead of 72: the
+            // sweep loop of the large one re-read ~ 30 coefficients from AGPRs and SGPR-spill lanes at the head of every sweep.  (Round 7: one
+            // instantiation per count beat <0, 4> / <0, 6> padded to their size, 125 against 129 us per launch, EXPERIMENTS.md.)
             int n_sweeps = 0;
             if constexpr (CORE == 1) core<0, 4>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
             else if constexpr (CORE == 2) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
@@ -312,8 +328,12 @@ template <bool CONE> struct RareSolver<LaneDev, CONE> {
             } else if (mA == 0 && mB <= 6) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
             else core<NA, NB>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
 #else
-            if (mA == 0 && mB <= 4) core<0, 4>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
-            else if (mA == 0 && mB <= 6) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            if (mA == 0 && mB <= 1) core<0, 1>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if (mA == 0 && mB == 2) core<0, 2>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if (mA == 0 && mB == 3) core<0, 3>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if (mA == 0 && mB == 4) core<0, 4>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if (mA == 0 && mB == 5) core<0, 5>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
+            else if (mA == 0 && mB == 6) core<0, 6>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
             else core<NA, NB>(cfg, w, a, b, rhs, dinv, diag, lam, lo, hi, grp, mA, mB, mu_e, track, thr, n_sweeps);
 #endif
             }

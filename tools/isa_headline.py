@@ -33,5 +33,22 @@ print(f"{name}: {len(f)} ISA lines, {len(scr)} scratch instructions ({sum(1 for 
 print("   per twentieth of the kernel: " + " ".join(f"{h.get(k, 0):3d}" for k in range(20)))
 meta = [l.strip() for l in lines if re.search(r"\.(sgpr|vgpr|agpr)_count|\.private_segment_fixed_size|vgpr_spill_count", l)]
 print("   " + "  ".join(meta[-5:]))   # (the step kernel is the file's last)
+# the many-rows solve's sweep loops (qs_rare.h core<>, the cone's): loops under 1000 instructions with v_med3, v_rsq and at least two
+# v_readlane per v_med3, one line per loop header
+isin = lambda l: bool(l.strip()) and not l.strip().startswith((";", ".", "//")) and not l.strip().endswith(":")
+labels = {m.group(1): i for i, l in enumerate(f) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
+sweeps = set()
+for i, l in enumerate(f):
+    m = re.search(r"s_cbranch_\w+ (\.LBB\d+_\d+)|s_branch (\.LBB\d+_\d+)", l)
+    t = m and (m.group(1) or m.group(2))
+    if t in labels and labels[t] < i:
+        body = f[labels[t]:i + 1]
+        c = lambda p: sum(1 for x in body if re.search(p, x))
+        n = sum(isin(x) for x in body)
+        if n < 1000 and c(r"v_med3") and c(r"v_readlane") >= 2 * c(r"v_med3") and c(r"v_rsq"):   # (the cone's friction pairs)
+            sweeps.add((labels[t], n, c(r"s_cbranch"), c(r"v_readlane"), c(r"s_nop"), c(r"v_med3"), c(r"\sscratch_")))
+print("many-rows sweep loops (innermost per header):")
+for at, n, br, rl, nop, med, sc in sorted(s for s in sweeps if not any(o[0] == s[0] and o[1] < s[1] for o in sweeps)):
+    print(f"   line {at}: {n} instructions, {br} s_cbranch, {rl} v_readlane, {nop} s_nop, {med} v_med3, {sc} scratch")
 sys.stdout.flush()
 subprocess.call([sys.executable, os.path.join(REPO, "tools", "hot_loop_isa.py"), out, name])
