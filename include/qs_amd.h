@@ -181,6 +181,18 @@ int qs_set_demo_counter(qs_handle* h, const uint8_t* mask, const int32_t* values
 int qs_step(qs_handle* h, const float* actions /*[N,action_dim]*/, float* obs /*[N,obs_dim]*/, float* rew /*[N]*/,
             uint8_t* done /*[N]*/, uint8_t* truncated /*[N]*/);
 int qs_get_state(qs_handle* h, float* state /*[N,37]*/);
+/* A push on the trunk (Quadruped.apply_external_force, quadruped.py:338-343: pybullet.applyExternalForce on link 0 at its centre of mass):
+ * force F and torque tau, acting at the trunk's centre of mass (its inertial origin), on the next `substeps` physics substeps each masked
+ * environment steps -- counted on the device, across env-step boundaries.  QS_FRAME_WORLD: the vectors are fixed in the world frame;
+ * QS_FRAME_LINK: fixed to the trunk, turning with it.  Setting a push again replaces the earlier one; substeps = 0 cancels it; a reset of the
+ * environment (auto-reset in a step, qs_reset, qs_reset_to) cancels it; qs_set_state keeps it; settles never see it.  pybullet clears external
+ * forces after every stepSimulation: the reference's apply_external_force is substeps = 1, QS_FRAME_LINK, tau = 0.
+ * Device pointers, stream-ordered, no host synchronisation: mask NULL = every environment, wrench [N,6] (F, tau), substeps [N].  Fails for an
+ * unknown frame.  A selected row with a negative duration or a non-finite value is not taken (the environment keeps its push); as checking
+ * device data here would synchronise, the refusal is reported by the next qs_stats or qs_counter (which wait for the device anyway): it
+ * fails once, naming the first refused environment. */
+enum { QS_FRAME_LINK = 1, QS_FRAME_WORLD = 2 };   /* pybullet.LINK_FRAME / WORLD_FRAME */
+int qs_set_external_wrench(qs_handle* h, const uint8_t* mask, const float* wrench /*[N,6]: F, tau*/, const int32_t* substeps /*[N]*/, int frame);
 int qs_set_state(qs_handle* h, const float* state /*[N,37]*/);
 enum {
     QS_INFO_FOOT_FORCE = 0, QS_INFO_FOOT_CONTACT = 1, QS_INFO_TORQUE = 2, QS_INFO_SPRING_TORQUE = 3, QS_INFO_TASK = 4,
@@ -192,6 +204,8 @@ enum {
                                   * six impulses of its fixed constraint at the last substep, the distance between the two pivots */
     QS_INFO_WRAPPER = 10,  /* [N,4]: phase after the step (0 policy, 1 take-off hold, 2 landing, 3 rest), scripted (the step just
                             * made ignored the caller's action), timer, end time */
+    QS_INFO_EXTERNAL_WRENCH = 14,  /* [N,8]: the push of qs_set_external_wrench: force 3, torque 3 (as set, in their frame), remaining substeps,
+                                    * frame */
 };
 int qs_info_dim(const qs_handle* h, int which);
 int qs_get_info(qs_handle* h, int which, float* out /*[N, qs_info_dim]*/);
@@ -319,8 +333,8 @@ const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
- * qs_config::reserved_f[0] became support_margin).  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
-#define QS_ABI_VERSION 5
+ * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH.  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+#define QS_ABI_VERSION 6
 int qs_abi_version(void);
 
 #ifdef __cplusplus

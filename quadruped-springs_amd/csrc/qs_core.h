@@ -919,6 +919,27 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         c.dv = mk3<V>(qsel(rare_mine, r.dv.x, c.dv.x), qsel(rare_mine, r.dv.y, c.dv.y), qsel(rare_mine, r.dv.z, c.dv.z));
     }
 
+    // An external push on the trunk (qs_set_external_wrench): force F and torque tau at the trunk's centre of mass c (its inertial origin,
+    // base frame), in the world frame (rotated into the base frame every substep) or fixed to the trunk.  As a generalized force on the base
+    // rows it is Q = [c x F_b + tau_b ; F_b], which H a = Q - C takes as the bias C minus Q: folded into f0, the base's own part of Cb.  The
+    // row acts on the substeps k < remaining of its env step.  Selected in, never added as a zero: an environment without a push keeps f0's
+    // bits, whatever its wave-mates do.  Everything downstream starts from the accelerations this bias gives: the
+    // common-path and the full build's contact rows (through v*), the many-rows solve, and the common-path build's predicted hand-over
+    // (its predicted velocities come from the same `ab`), so a push that throws a link at the ground is seen coming like any other fall.
+    static QS_FN void push_wrench(const float* push, int k, const V* R, Spv& f0) {
+        using namespace go1;
+        const V Fx = T::ld(push, 0), Fy = T::ld(push, 1), Fz = T::ld(push, 2), Tx = T::ld(push, 3), Ty = T::ld(push, 4), Tz = T::ld(push, 5);
+        const M on = qlt(V((float)k), T::ld(push, 6)), world = qgt(T::ld(push, 7), V(1.5f));
+        V3v Fb, Tb;
+        Fb.x = qsel(world, R[0] * Fx + R[3] * Fy + R[6] * Fz, Fx); Tb.x = qsel(world, R[0] * Tx + R[3] * Ty + R[6] * Tz, Tx);
+        Fb.y = qsel(world, R[1] * Fx + R[4] * Fy + R[7] * Fz, Fy); Tb.y = qsel(world, R[1] * Tx + R[4] * Ty + R[7] * Tz, Ty);
+        Fb.z = qsel(world, R[2] * Fx + R[5] * Fy + R[8] * Fz, Fz); Tb.z = qsel(world, R[2] * Tx + R[5] * Ty + R[8] * Tz, Tz);
+        const V3v m = cross(mk3<V>(V(TRUNK_CX), V(0.0f), V(TRUNK_CZ)), Fb);
+        const V Qx = m.x + Tb.x, Qy = m.y + Tb.y, Qz = m.z + Tb.z;
+        f0.a.x = qsel(on, f0.a.x - Qx, f0.a.x); f0.a.y = qsel(on, f0.a.y - Qy, f0.a.y); f0.a.z = qsel(on, f0.a.z - Qz, f0.a.z);
+        f0.l.x = qsel(on, f0.l.x - Fb.x, f0.l.x); f0.l.y = qsel(on, f0.l.y - Fb.y, f0.l.y); f0.l.z = qsel(on, f0.l.z - Fb.z, f0.l.z);
+    }
+
     // `detect`: classify the contacts of the non-foot links, the payload block and the link-link pairs (o.n_invalid).  The reference reads
     // GetContactInfo after the LAST stepSimulation of an env step (task_base.py:137-147 via gym_env.py:241-245), so the callers ask for it
     // there only -- unless cfg.body_contacts, where those links' heights decide in every substep whether they push back.
@@ -934,8 +955,10 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     // the substep boundary instead of letting the next substep run into its vote (round 6: that vote sits behind the substep's dynamics --
     // 10 k cycles of a 16 k substep, thrown away on the path of the wave every launch waits for).  A wrong guess costs time only: results
     // do not depend on where the switch happens (Env::step).
+    // `push` (null unless the step's wave has a push pending: wave-uniform): this environment's row of qs_set_external_wrench -- force 3,
+    // torque 3, remaining substeps at the start of the env step, frame -- and `push_k` the substep's index in its env step
     static QS_FN int substep(const qs_config& cfg, const Par& Pr, State& s, const V* tau, Out& o, bool detect = true, float* blk = nullptr, float* scratch_row = nullptr,
-                              bool last = true) {
+                              bool last = true, const float* push = nullptr, int push_k = 0) {
         using namespace go1;
         if (HOT && !SOFT && cfg.payload_soft) return 1;   // this build holds no payload rows
         bool hand_over_next = false;
@@ -1008,6 +1031,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         Spv fs2 = f2 + f3, fs1 = f1 + fs2;
         V C1 = dot(S1, fs1), C2 = dot(S2, fs2), C3 = dot(S3j, f3);
         Spv f0 = crf_add(apply(Pr.I0, a0), v0, apply(Pr.I0, v0));
+        if (push) push_wrench(push, push_k, R, f0);
         V Cb[6] = {T::quad_sum(fs1.a.x) + f0.a.x, T::quad_sum(fs1.a.y) + f0.a.y, T::quad_sum(fs1.a.z) + f0.a.z,
                    T::quad_sum(fs1.l.x) + f0.l.x, T::quad_sum(fs1.l.y) + f0.l.y, T::quad_sum(fs1.l.z) + f0.l.z};
         QS_PHASE(4)

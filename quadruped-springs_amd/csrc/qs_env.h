@@ -464,6 +464,9 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     // regular step, so a wave of settling records costs what a wave of environments costs and shares its instructions.
     // `trace` (null except in the lanes of a traced environment; `any_trace` is the wave-uniform "some lane has one") receives
     // one row per substep (qs_set_trace).
+    // `push` (null for the whole wave, or for none of it): this environment's row of qs_set_external_wrench (Sim::push_wrench), which acts on
+    // the substeps k < its remaining count -- counted from the start of the env step, so a resumed step<true> applies exactly those left.
+    // The caller counts the row down behind the step.
     static QS_FN void write_trace(float* row, float time, const typename S::State& s, const typename S::Out& o) {
         T::st(row, TR_TIME, V(time));
         T::st(row, TR_POS, s.pos.x); T::st(row, TR_POS + 1, s.pos.y); T::st(row, TR_POS + 2, s.pos.z);
@@ -520,7 +523,8 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     }
     template <bool RESUME = false, bool LEAN = false>
     static QS_FN StepOut step(const qs_config& cfg, float* rec, const float* act_row, float* obs, uint32_t env_id, int settle_n = 0,
-                              float* trace = nullptr, bool any_trace = false, const float* demo_rows = nullptr, int demo_len = 0, int resume_k = 0) {
+                              float* trace = nullptr, bool any_trace = false, const float* demo_rows = nullptr, int demo_len = 0, int resume_k = 0,
+                              const float* push = nullptr) {
         static_assert(!(RESUME && HOT), "an env step resumes in the full build");
         typename S::State s; typename S::Par P; typename S::Out o;
         if (RESUME) T::sync();   // (the stash was written by other lanes of the quad)
@@ -659,6 +663,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         _Pragma("unroll") for (int j = 0; j < 3; j++) old_tau[j] = T::ld_leg(rec, R_NEW_TAU + j, 3);
         if (!RESUME) { QS_LOAD_COUNTERS }
         const int n_sub = settle_n > 0 ? settle_n : cfg.action_repeat;
+        if (settle_n > 0) push = nullptr;   // (a settle never sees a push)
         float* const blk = cfg.payload_soft ? rec + R_BLOCK : nullptr;
         if (HOT) {
             // what a resumed step needs of the prologue goes into the (still unused) observation row here, once per step and whether or not
@@ -690,7 +695,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
             QS_PHASE_SUB_BEGIN
             if (LEAN) load_par_lean(rec, obs, P);
             S::actuate(cfg, P, s, cmd, o, tau, settle_n > 0);
-            const int rc = S::substep(cfg, P, s, tau, o, k == n_sub - 1 || cfg.body_contacts, blk, obs, k == n_sub - 1);
+            const int rc = S::substep(cfg, P, s, tau, o, k == n_sub - 1 || cfg.body_contacts, blk, obs, k == n_sub - 1, push, k);
             if (__builtin_expect(rc == 1, 0)) { gave_up = true; break; }
             QS_PHASE_SUB(k)
             if (__builtin_expect(any_trace, 0)) {

@@ -167,13 +167,15 @@ struct DemoTab { const float* rows; int length; };   // qs_set_demo: the demonst
 // observation) behind the result block, so that ONE device-to-host copy brings everything a VecEnv.step_wait returns.  The list's
 // fill count alternates between two counters: a step counts in cnt[parity] and clears the other one for the next step.
 struct TermTail { float* rows; int cap, parity; };
+// qs_set_external_wrench: rows [N][QS_PUSH_F] = force 3, torque 3 (as set, in their frame), remaining substeps, frame.  `rows` is null in a launch
+// where no push can be pending (the host knows: no push set since the last reset of every environment): the step then reads nothing of it.
+struct PushTab { float* rows; };
+enum { QS_PUSH_F = 8, QS_PUSH_REM = 6, QS_PUSH_FRAME = 7 };
 enum { CTL_SETTLE_SUBSTEPS = 0, CTL_RESETS = 1, CTL_SERVED = 2, CTL_SETTLED = 3, CTL_BACKLOG = 4, CTL_STALLS = 6,
        CTL_R = 8 /* one per cohort */, CTL_TERM_CNT = 8 + QS_COHORTS /* two */, CTL_DEV = 10 + QS_COHORTS /* QS_DEVCTR_*: the rare paths' telemetry */,
-#if defined(QS_PROBE_LAZY) || defined(QS_PROBE_SWEEPS) || defined(QS_PROBE_WARM)
-       CTL_N = 12 + QS_COHORTS + 10 /* the counting builds' counters (qs_core.h, tools/probe_*.py) */ };
-#else
-       CTL_N = 12 + QS_COHORTS };
-#endif
+       /* (CTL_DEV + 2 .. + 11: the counting builds' counters, qs_core.h, tools/probe_*.py) */
+       CTL_PUSH_REFUSED = 22 + QS_COHORTS /* 1 + the first environment whose row qs_set_external_wrench refused, 0 if none */,
+       CTL_N = 23 + QS_COHORTS };
 
 // settled-state fields a look-ahead reset copies into the record (everything the 2500-substep settle determines), and the slot's tag.
 // Every load is issued before the first value is used: as four rolled loops (`rec[i] = src[i]`) the copy was a load, a wait and an LDS write
@@ -261,7 +263,8 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
                                                  float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
                                                  uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep,
                                                  float* __restrict__ term_obs, LookAhead la,
-                                                 unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail) {
+                                                 unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail,
+                                                 PushTab push) {
     // the friction model is compiled in (qs_config::friction_cone picks the kernel at launch).  Everything of the full build is inlined in
     // both kernels: as real functions (round 2) the many-rows solvers took State / Out by reference, which kept them in memory around the
     // call, and expressions that then span a store and a load are no longer contracted into the FMAs the common-path build forms -- a wave
@@ -297,6 +300,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
     // the quad of an environment fetches its action row (lane l takes entries l, l + 4, l + 8) -- issued before the tile loads, whose
     // latency then covers it
     float a_pre[3] = {0.0f, 0.0f, 0.0f};
+    float p_rem = 0.0f;                                                  // substeps of a push left at the start of this step (settle lanes: none)
     int2 job = make_int2(0, 0);                                          // settle lanes: whose reset this record is (environment, episode)
     if (!settling) {
 #pragma unroll
@@ -304,6 +308,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
             const int k = (int)(threadIdx.x & 3u) + 4 * j;
             if (k < d && valid) a_pre[j] = actions[(size_t)env * d + k];
         }
+        if (push.rows && valid) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
     } else job = lanes.stage_jobs[valid ? env : first];
     const bool spawn = settling && lanes.spawn[cohort], last = settling && lanes.last[cohort];
     const int load_extent = settling ? (spawn ? 0 : (cfg.payload_soft ? (int)TILE_ALL : (int)QS_SETTLE_END)) : tile_extent(cfg, false);
@@ -330,15 +335,19 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
     const bool any_trace = tap.rows != nullptr && !settling && tap.env >= first && tap.env < first + QS_ENVS_PER_WAVE;   // wave-uniform
     QS_PHASE(13)
     float* const trow = any_trace && env == tap.env ? tap.rows : nullptr;
+    // wave-uniform: some environment of the wave has a push pending; then every quad reads its own row in the substeps (wave-mates without a
+    // push select nothing of it, Sim::push_wrench)
+    const bool any_push = push.rows != nullptr && __any(p_rem > 0.0f);
+    const float* const prow = any_push ? push.rows + (size_t)(valid ? env : first) * QS_PUSH_F : nullptr;
     // The env step starts in the common-path build; a wave in which some environment needs a rare path goes on in the full build from the
     // substep where that shows (Env::step: the state of that moment is in the LDS record, the prologue's results in the observation row).
     // A payload_soft handle under the friction pyramid has its block's rows in no common-path build: its first substep already hands over.
     typename E::StepOut r;
     {
-        const typename EH::StepOut rh = EH::template step<false, QS_LEAN_WAVES(WAVES)>(cfg, rec, s_act + slot * 12, ob, gid, settle_n, trow, any_trace, demo.rows, demo.length);
+        const typename EH::StepOut rh = EH::template step<false, QS_LEAN_WAVES(WAVES)>(cfg, rec, s_act + slot * 12, ob, gid, settle_n, trow, any_trace, demo.rows, demo.length, 0, prow);
         r.reward = rh.reward; r.done = rh.done; r.trunc = rh.trunc; r.resume = rh.resume;
     }
-    if (__builtin_expect(r.resume >= 0, 0)) r = E::template step<true>(cfg, rec, s_act + slot * 12, ob, gid, settle_n, trow, any_trace, demo.rows, demo.length, r.resume);
+    if (__builtin_expect(r.resume >= 0, 0)) r = E::template step<true>(cfg, rec, s_act + slot * 12, ob, gid, settle_n, trow, any_trace, demo.rows, demo.length, r.resume, prow);
     QS_PHASE(14)
     if (settling) {
         if (valid && (threadIdx.x & 3) == 0) atomicAdd(&stats[CTL_SETTLE_SUBSTEPS], (unsigned long long)settle_n);
@@ -350,6 +359,9 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
         return;
     }
     const bool dn = r.done > 0.5f;
+    // the push counts down by the step's substeps; an episode that ended (its auto-reset below, or the caller's reset) cancels it
+    if (any_push && valid && p_rem > 0.0f && (threadIdx.x & 3) == 0)
+        push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM] = dn ? 0.0f : fmaxf(p_rem - (float)cfg.action_repeat, 0.0f);
     if (valid && (threadIdx.x & 3) == 0) {
         if (rew_out) { rew_out[env] = r.reward; done_out[env] = dn ? 1 : 0; trunc_out[env] = r.trunc > 0.5f ? 1 : 0; }
         else {   // fused layout (qs_step_fused): one row [obs | reward | done + 2 * truncated] per environment
@@ -416,8 +428,9 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
 
 #define QS_STEP_ARGS const qs_config* __restrict__ cfgp, float* __restrict__ recs, const float* __restrict__ actions, float* __restrict__ obs_out,    \
                      float* __restrict__ rew_out, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep, \
-                     float* __restrict__ term_obs, LookAhead la, unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail
-#define QS_STEP_PASS cfgp, recs, actions, obs_out, rew_out, done_out, trunc_out, obs_keep, term_obs, la, stats, lanes, tap, demo, tail
+                     float* __restrict__ term_obs, LookAhead la, unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail, \
+                     PushTab push
+#define QS_STEP_PASS cfgp, recs, actions, obs_out, rew_out, done_out, trunc_out, obs_keep, term_obs, la, stats, lanes, tap, demo, tail, push
 // One wave per SIMD: the whole 512-entry register file (256 VGPR + 256 AGPR) for one wave.  The common-path substep loop holds no scratch
 // instruction (tools/isa_headline.py); the cold code behind it -- the full build's substeps of a handed-over step, the in-step settle --
 // spills (~110 values, ~470 B of scratch per lane).  The launch time is one wave's instruction stream, so this is the variant while the
@@ -510,7 +523,8 @@ __global__ void k_lookahead_requeue(unsigned long long* __restrict__ ctl, LookAh
 // takes it; the others settle side by side.
 template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
                                                       const uint8_t* __restrict__ mask, float* __restrict__ obs_keep,
-                                                      unsigned long long* __restrict__ stats, const float* __restrict__ states, LookAhead la) {
+                                                      unsigned long long* __restrict__ stats, const float* __restrict__ states, LookAhead la,
+                                                      float* __restrict__ push_rows) {
     using E = Env<LaneDev, CONE>;
     __shared__ __attribute__((aligned(16))) float s_rec[QS_TILE_FLOATS];
     __shared__ __attribute__((aligned(16))) float s_obs[QS_ENVS_PER_WAVE * QS_MAX_OBS];
@@ -531,6 +545,7 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const
         if (states == nullptr) ahead = lookahead_take(la, stats, rec, env, qs::f2i(rec[R_EPISODE]) + 1, cfg.payload_soft != 0);
         else if (la.K > 0 && (threadIdx.x & 3) == 0) la.cur[env] = qs::f2i(rec[R_EPISODE]) + 1;   // (the look-ahead window moves on all the same)
         if ((threadIdx.x & 3) == 0) atomicAdd(&stats[CTL_RESETS], 1ull);
+        if ((threadIdx.x & 3) == 0) push_rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM] = 0.0f;   // a reset cancels the environment's push
     }
     bool write_back = false;
     if (states) {   // reference-state initialisation (gym_env.py:278-297 with robot_desired_state set): randomizers, then the given
@@ -660,6 +675,8 @@ struct qs_handle {
     long long tick;         // qs_step launches since the settle lanes were switched on
     float* trace_rows; int trace_env;
     float* d_demo; int demo_len;   // qs_set_demo
+    float* d_push;          // [N][QS_PUSH_F]: qs_set_external_wrench
+    int push_live;          // a push may be pending: the step launches read d_push (cleared by a reset of every environment)
     int n_simd, step_variant;   // SIMDs of the device; 0 = pick k_step / k_step_dense by grid size, 1 / 2 = forced (QS_STEP_VARIANT)
     unsigned long long* d_stats;
     TermTail tail;          // set for the launch of a host-path step
@@ -750,6 +767,7 @@ static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
     QS_HIP(hipMalloc(&h->d_obs, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMalloc(&h->d_term_obs, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMalloc(&h->d_stats, CTL_N * sizeof(unsigned long long)));
+    QS_HIP(hipMalloc(&h->d_push, n * QS_PUSH_F * sizeof(float)));
     {
         QsDevCfg dc;
         dc.cfg = h->cfg; dc.counters = h->d_stats + CTL_DEV;
@@ -758,6 +776,7 @@ static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
     QS_HIP(hipMemset(h->d_obs, 0, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMemset(h->d_term_obs, 0, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMemset(h->d_stats, 0, CTL_N * sizeof(unsigned long long)));
+    QS_HIP(hipMemset(h->d_push, 0, n * QS_PUSH_F * sizeof(float)));
     QS_HIP(hipEventCreate(&h->ev0));
     QS_HIP(hipEventCreate(&h->ev1));
     hipLaunchKernelGGL(k_init, dim3(n_waves(cfg->n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec);
@@ -803,6 +822,7 @@ void qs_destroy(qs_handle* h) {   // also used on a partially built handle (null
     if (h->d_staging) hipFree(h->d_staging);
     if (h->d_stage_jobs) hipFree(h->d_stage_jobs);
     if (h->d_demo) hipFree(h->d_demo);
+    if (h->d_push) hipFree(h->d_push);
     host_path_free(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -834,18 +854,20 @@ int qs_enable_timing(qs_handle* h, int on) {
 int qs_reset(qs_handle* h, const uint8_t* mask) {
     if (!h) QS_FAIL(-1, "null handle");
     QS_ON_DEVICE(h);
-    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la);
-    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la);
+    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la, h->d_push);
+    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la, h->d_push);
     QS_HIP(hipGetLastError());
+    if (!mask) h->push_live = 0;   // every push is cancelled
     return 0;
 }
 
 int qs_reset_to(qs_handle* h, const uint8_t* mask, const float* states) {
     if (!h || !states) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la);
-    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la);
+    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la, h->d_push);
+    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la, h->d_push);
     QS_HIP(hipGetLastError());
+    if (!mask) h->push_live = 0;
     return 0;
 }
 
@@ -891,6 +913,7 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     if (E::demo_task(h->cfg.task) && !h->d_demo) QS_FAIL(-1, "the DEMO tasks need a demonstration: qs_set_demo first");
     TermTail tail = h->tail;
     memset(&h->tail, 0, sizeof(h->tail));       // (set by qs_host_step_begin for its own launch only)
+    PushTab push; push.rows = h->push_live ? h->d_push : nullptr;
     int grid = lanes.n_env_waves;
     bool lanes_fit = true;      // the environments' waves and the lanes' usual share fit the SIMDs
     if (h->la.K > 0 && h->lanes_on) {
@@ -932,7 +955,7 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     const bool dense = h->step_variant == 2 || (h->step_variant == 0 && (lanes.n_env_waves > h->n_simd || !lanes_fit));
     const size_t lds = (size_t)QS_ENVS_PER_WAVE * ((h->cfg.payload_soft ? QS_REC_END : QS_INFO_END) + QS_MAX_OBS + 12) * sizeof(float);
 #define QS_LAUNCH_STEP(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(QS_WAVE), lds, h->stream, h->d_cfg, h->d_rec, actions, obs, rew, done, trunc, \
-                                                 h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail)
+                                                 h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push)
 #define QS_PICK(C, S) { if (dense) QS_LAUNCH_STEP((k_step_dense<C, S>)); else QS_LAUNCH_STEP((k_step<C, S>)); }
     if (h->cfg.friction_cone && h->cfg.payload_soft) QS_PICK(true, true)
     else if (h->cfg.friction_cone) QS_PICK(true, false)
@@ -1151,6 +1174,44 @@ int qs_set_demo_counter(qs_handle* h, const uint8_t* mask, const int32_t* values
     return 0;
 }
 
+// a row whose duration is negative or whose wrench is not finite is not taken (the environment keeps what it had) and is recorded in
+// CTL_PUSH_REFUSED: checking device data in qs_set_external_wrench would synchronise, so the refusal is reported by the next call that waits
+// for the device anyway (push_refusal)
+__global__ void k_set_wrench(float* __restrict__ rows, int n, const uint8_t* __restrict__ mask, const float* __restrict__ wrench,
+                             const int32_t* __restrict__ substeps, int frame, unsigned long long* __restrict__ refused) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n || (mask && !mask[e])) return;
+    float w[6];
+    bool ok = substeps[e] >= 0;
+    for (int i = 0; i < 6; i++) { w[i] = wrench[(size_t)e * 6 + i]; ok = ok && (__float_as_uint(w[i]) & 0x7f800000u) != 0x7f800000u; }   // (bits: -ffinite-math-only folds isfinite)
+    if (!ok) { atomicCAS(refused, 0ull, (unsigned long long)e + 1ull); return; }
+    const int k = min(substeps[e], 1 << 24);    // (a count a float holds exactly: 4.6 hours of physics at dt = 1 ms)
+    float* r = rows + (size_t)e * QS_PUSH_F;
+    for (int i = 0; i < 6; i++) r[i] = w[i];
+    r[QS_PUSH_REM] = (float)k; r[QS_PUSH_FRAME] = (float)frame;
+}
+
+int qs_set_external_wrench(qs_handle* h, const uint8_t* mask, const float* wrench, const int32_t* substeps, int frame) {
+    if (!h || !wrench || !substeps) QS_FAIL(-1, "null argument");
+    if (frame != QS_FRAME_LINK && frame != QS_FRAME_WORLD) QS_FAIL(-1, "unknown frame %d (QS_FRAME_LINK = 1, QS_FRAME_WORLD = 2)", frame);
+    QS_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_set_wrench, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_push, h->cfg.n_envs, mask, wrench, substeps, frame,
+                       h->d_stats + CTL_PUSH_REFUSED);
+    QS_HIP(hipGetLastError());
+    h->push_live = 1;
+    return 0;
+}
+
+// after a synchronisation: fails once if qs_set_external_wrench refused a row since the last report
+static int push_refusal(qs_handle* h) {
+    unsigned long long v = 0;
+    QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_PUSH_REFUSED], sizeof(v), hipMemcpyDeviceToHost));
+    if (v == 0) return 0;
+    QS_HIP(hipMemset(&h->d_stats[CTL_PUSH_REFUSED], 0, sizeof(v)));
+    QS_FAIL(-1, "qs_set_external_wrench refused the row of environment %llu (and maybe others): a negative duration or a non-finite force / "
+                "torque; those environments kept their earlier push", v - 1);
+}
+
 int qs_set_trace(qs_handle* h, int env, float* rows) {
     if (!h) QS_FAIL(-1, "null handle");
     if (env >= h->cfg.n_envs) QS_FAIL(-1, "trace environment %d out of range (%d environments)", env, h->cfg.n_envs);
@@ -1175,6 +1236,7 @@ int qs_counter(qs_handle* h, int which, uint64_t* value) {
     if (!h || !value) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
     QS_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = push_refusal(h)) return rc;
     unsigned long long v = 0;
     switch (which) {
     case QS_COUNTER_SETTLE_SUBSTEPS: QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_SETTLE_SUBSTEPS], sizeof(v), hipMemcpyDeviceToHost)); break;
@@ -1281,6 +1343,7 @@ int qs_info_dim(const qs_handle* h, int which) {
     case QS_INFO_FILTERED_ACTION: return 12;
     case QS_INFO_REWARD_END: return 1;
     case QS_INFO_PAYLOAD_BLOCK: return QS_BLOCK_DIM;
+    case QS_INFO_EXTERNAL_WRENCH: return QS_PUSH_F;
     default: return -1;
     }
 }
@@ -1312,6 +1375,9 @@ int qs_get_info(qs_handle* h, int which, float* out) {
         hipLaunchKernelGGL(k_task_info, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_rec, h->cfg.n_envs, out, (int)E::demo_task(h->cfg.task), h->cfg.info_fields);
         QS_HIP(hipGetLastError());
         return 0;
+    case QS_INFO_EXTERNAL_WRENCH:
+        QS_HIP(hipMemcpyAsync(out, h->d_push, (size_t)h->cfg.n_envs * QS_PUSH_F * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        return 0;
     case QS_INFO_TERMINAL_OBS:
         QS_HIP(hipMemcpyAsync(out, h->d_term_obs, (size_t)h->cfg.n_envs * h->cfg.obs_dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         return 0;
@@ -1338,6 +1404,7 @@ int qs_stats(qs_handle* h, uint64_t* settle_substeps, uint64_t* resets) {
     QS_ON_DEVICE(h);
     unsigned long long v[2];
     QS_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = push_refusal(h)) return rc;
     QS_HIP(hipMemcpy(v, h->d_stats, sizeof(v), hipMemcpyDeviceToHost));
     if (settle_substeps) *settle_substeps = v[0];
     if (resets) *resets = v[1];

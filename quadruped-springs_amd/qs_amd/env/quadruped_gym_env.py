@@ -148,6 +148,11 @@ class _RobotView:
     def set_spring_damping(self, b):
         self._env._vec.set_params("spring_b", np.asarray(b, np.float32)[None])
 
+    def apply_external_force(self, force):                 # quadruped.py:338-343
+        """Apply an external force on the quadruped COM: pybullet's applyExternalForce on the trunk at its centre of mass in LINK_FRAME,
+        which pybullet clears after the next stepSimulation -- a push of one physics substep, in the trunk's frame."""
+        self._env._vec.apply_external_force(np.asarray(force, np.float32).reshape(3), substeps=1, frame="link")
+
 
 class _MotorModelView:
     """`robot._motor_model._kp / _kd`: the gains the reference's wrappers swap temporarily (landing_wrapper.py:18-37)."""

@@ -13,9 +13,10 @@ from .config import DEMO_FILES, OBSERVATION_EPS, build_config
 from .spaces import Box, SB3VecEnv
 
 INFO = dict(foot_force=0, foot_contact=1, torque=2, spring_torque=3, task=4, n_invalid=5, params=6, counters=7,
-            last_action=8, terminal_obs=9, wrapper=10, filtered_action=11, reward_end=12, payload_block=13)
+            last_action=8, terminal_obs=9, wrapper=10, filtered_action=11, reward_end=12, payload_block=13, external_wrench=14)
 PHASE = ("policy", "take_off", "landing", "rest")
 PARAM = dict(mu=0, spring_k=1, spring_b=2, kp=3, kd=4, all=5)
+FRAME = dict(link=1, world=2)   # QS_FRAME_LINK / QS_FRAME_WORLD = pybullet.LINK_FRAME / WORLD_FRAME
 
 
 class QuadrupedVecEnv(SB3VecEnv):
@@ -71,6 +72,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         self._terminal_hook = None     # DeviceVecNormalize.step_async: normalises the per-environment terminal observations (overflow of the compact list)
         self.copy_outputs = bool(copy_outputs)
         self._trace = None
+        self._push_keep = None        # the inputs of the last apply_external_force, alive until its kernel has read them
         self.render_mode = None
         self.demo_list, self.demo_length = None, 0
         if load_demo and self.meta["task_env"] in DEMO_FILES:
@@ -170,6 +172,82 @@ class QuadrupedVecEnv(SB3VecEnv):
         self._stream()
         _lib.check(self.lib.qs_set_params(self.h, k, self._ptr(v)))
         self.torch.cuda.current_stream(self.device).synchronize()  # `v` may be a temporary
+
+    def apply_external_force(self, force, torque=None, substeps=None, frame="world", indices=None):
+        """Push the trunks (Quadruped.apply_external_force, quadruped.py:338-343, batched): force [N,3] or [3] (N), torque likewise (N m,
+        default 0), acting at each trunk's centre of mass on the next `substeps` physics substeps of the environment (None = one env
+        step, action_repeat substeps; an int or [N] ints; 0 cancels), counted on the device across env steps.  frame "world": the vectors
+        stay fixed in the world frame; "link": they are fixed to the trunk and turn with it.  indices: the environments pushed (None = all);
+        the others keep what they had.  A new push replaces an environment's earlier one; a reset cancels it.
+        Accepts numpy arrays, lists, host tensors or tensors on the device, and never waits for the device: host data is checked here and
+        goes over through page-locked staging without blocking (so a learner may push every step); device tensors are checked by the
+        kernel, and a refused row (negative duration, non-finite value) is reported by the next call that waits for the device anyway
+        (stats() or counter() raise; include/qs_amd.h)."""
+        t = self.torch
+        if frame not in FRAME:
+            raise ValueError(f"frame must be one of {sorted(FRAME)}, got {frame!r}")
+        n = self.num_envs
+        keep = []
+
+        def to_device(a):
+            """a host array onto the device without a synchronous copy: page-locked staging (the caching host allocator keeps the staging
+            block until the copy on the stream has read it), then an asynchronous copy"""
+            h = t.from_numpy(np.ascontiguousarray(a))
+            if self.device.type == "cpu":
+                return h
+            h = h.pin_memory()
+            keep.append(h)
+            return h.to(self.device, non_blocking=True)
+
+        def rows(x, name):
+            if isinstance(x, t.Tensor) and x.device == self.device:
+                v = x.to(dtype=t.float32)
+                if v.shape not in ((3,), (n, 3)):
+                    raise ValueError(f"{name} must have shape (3,) or {(n, 3)}, got {tuple(v.shape)}")
+            else:
+                a = (x.detach().cpu().numpy() if isinstance(x, t.Tensor) else np.asarray(x)).astype(np.float32)
+                if a.shape not in ((3,), (n, 3)):
+                    raise ValueError(f"{name} must have shape (3,) or {(n, 3)}, got {tuple(a.shape)}")
+                if not np.all(np.isfinite(a)):
+                    raise ValueError(f"{name} must be finite")
+                v = to_device(a)
+            return v.expand(n, 3)
+
+        self._stream()
+        f = rows(force, "force")
+        tq = t.zeros((n, 3), dtype=t.float32, device=self.device) if torque is None else rows(torque, "torque")
+        w = t.cat([f, tq], dim=1).contiguous()
+        k = self.cfg.action_repeat if substeps is None else substeps
+        if isinstance(k, t.Tensor) and k.device == self.device:
+            if k.dtype.is_floating_point or k.dtype == t.bool:
+                raise ValueError(f"substeps must be an integer tensor, got {k.dtype}")
+            k = k.to(dtype=t.int32)
+            if k.shape not in ((), (n,)):
+                raise ValueError(f"substeps must be a scalar or have shape {(n,)}, got {tuple(k.shape)}")
+            k = k.expand(n)
+        else:
+            a = k.detach().cpu().numpy() if isinstance(k, t.Tensor) else np.asarray(k)
+            if a.dtype.kind not in "iu" or np.any(a < 0):
+                raise ValueError(f"substeps must be a non-negative integer (or [N] of them), got {k!r}")
+            if a.shape not in ((), (n,)):
+                raise ValueError(f"substeps must be a scalar or have shape {(n,)}, got {tuple(a.shape)}")
+            if np.any(a > 2 ** 31 - 1):
+                raise ValueError("substeps must fit an int32")
+            k = t.full((n,), int(a), dtype=t.int32, device=self.device) if a.shape == () else to_device(a.astype(np.int32))
+        k = k.contiguous()
+        m = None
+        if indices is not None:
+            if isinstance(indices, t.Tensor) and indices.device == self.device:
+                # (index_fill_ takes the value as a kernel argument; `m[idx] = 1` stages a host scalar and synchronises)
+                m = t.zeros(n, dtype=t.uint8, device=self.device).index_fill_(0, indices.to(t.int64), 1)
+            else:
+                mh = np.zeros(n, np.uint8)
+                mh[np.asarray(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices), np.int64)] = 1
+                m = to_device(mh)
+        _lib.check(self.lib.qs_set_external_wrench(self.h, None if m is None else self._ptr(m), self._ptr(w), self._ptr(k), FRAME[frame]))
+        # (everything here is ordered on the current stream; the references keep the device buffers from going back to the caching
+        # allocator before the kernel has read them, the staging blocks are held by the host allocator until their copies are done)
+        self._push_keep = (w, k, m, keep)
 
     def stats(self):
         a, b = C.c_uint64(), C.c_uint64()
