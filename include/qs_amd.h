@@ -17,6 +17,7 @@
  *   qs_get_info    GetContactInfo, GetMotorTorques, task scalars  env/quadruped.py:209-258, env/tasks/task_base.py:44-59
  *   qs_set_params  set_spring_stiffness/damping, changeDynamics(lateralFriction), kp/kd swaps of the landing wrappers
  *                                                                 env/quadruped.py:732-742, env/wrappers/landing_wrapper.py:22-30
+ *   qs_render      QuadrupedGymEnv.render(mode="rgb_array")      env/quadruped_gym_env.py:334-335, utils/camera.py:35-59
  *
  * Conventions
  *   - plain pointers and sizes only; all array arguments are DEVICE pointers (HIP) owned by the caller, row-major,
@@ -329,12 +330,43 @@ int qs_norm_step_io(qs_norm* h, const qs_norm_io* io, int training, int norm_obs
  * observation width or another device than `h`. */
 int qs_host_set_norm(qs_handle* h, qs_norm* norm, int training, int norm_obs, int norm_reward, float* raw_obs, float* raw_rew);
 
+/* ---- Camera images (QuadrupedGymEnv.render(mode="rgb_array") -> utils/camera.py:35-59, which calls pybullet.getCameraImage with
+ * computeViewMatrixFromYawPitchRoll(target, distance, yaw, pitch, roll 0, upAxisIndex 2) and computeProjectionMatrixFOV(fov, W / H, near,
+ * far)).  Every environment is its own world: its image shows its robot (the collision primitives of go1.urdf -- trunk box, hip housings,
+ * thigh-shoulder cylinders, thigh and calf boxes, foot spheres -- posed by the state row, plus the payload block when the parameters carry
+ * a payload mass > 0), the plane z = 0 as a checkerboard of 1 m squares and a constant sky; one directional light, Lambert shading plus
+ * ambient, hard shadows cast by the robot; one ray through each pixel centre (row 0 at the top).  Camera: R = Rz(yaw) Rx(pitch) (degrees),
+ * eye = target + R (0, -distance, 0), up = R (0, 0, 1), looking at the target, fov vertical; hits nearer than near_clip along the view axis
+ * are ignored and nothing beyond far_clip is drawn.  (Our reading of Bullet's C API; camera modes: qs_amd/render.py CAMERA_MODES.)
+ * Outputs, row-major [m, height, width]: rgba packed RGBA8 (R in the low byte, A = 255); depth (may be NULL) in metres along the view axis,
+ * far_clip for sky; seg (may be NULL) int32: -1 sky, 0 ground, 1 trunk, 2 + 4 leg + part (legs in q order; part 0 hip, 1 thigh box and
+ * shoulder cylinder, 2 calf, 3 foot), 18 payload block.  A pixel depends on its environment's state, the camera and the image size only.
+ * Fails (nothing launched) for m < 0, width or height outside [1, 8192], a null rgba, fov_deg outside (0, 180) or 0 < near_clip < far_clip
+ * not holding.  Stream-ordered, no host synchronisation, no allocation. */
+typedef struct qs_camera {
+    float target[3];      /* world position; with follow_base: an offset added to the base position */
+    float distance, yaw_deg, pitch_deg, fov_deg, near_clip, far_clip;
+    int32_t follow_base;  /* 1: target = base position + target */
+    int32_t draw_payload; /* 0: leave the payload block out */
+} qs_camera;
+/* The handle's environments env_ids[0..m) (device int32), read straight from the records, on the handle's stream.  Under cfg.payload_soft
+ * the block is drawn at its own pose.  An id outside [0, n_envs) draws sky with segmentation id -2, and the next qs_stats or qs_counter
+ * (which wait for the device anyway) fails once, naming its position in env_ids. */
+int qs_render(qs_handle* h, const int32_t* env_ids, int m, const qs_camera* cam, int width, int height,
+              uint32_t* rgba /*[m,H,W]*/, float* depth /*[m,H,W] or NULL*/, int32_t* seg /*[m,H,W] or NULL*/);
+/* Any [m,37] state rows in device memory (qs_get_state layout), e.g. a recorded rollout or the trace tap's rows; params [m,24] (layout of
+ * QS_INFO_PARAMS; the payload block sits at r_payload in the base frame) or NULL (no payload block).  On `stream` (a hipStream_t, NULL = the
+ * null stream) of the current device. */
+int qs_render_states(const float* states, const float* params, int m, const qs_camera* cam, int width, int height,
+                     uint32_t* rgba, float* depth, int32_t* seg, void* stream);
+
 const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
- * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH.  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
-#define QS_ABI_VERSION 6
+ * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states.  A binding compares it with the
+ * QS_ABI_VERSION of the header it was written against. */
+#define QS_ABI_VERSION 7
 int qs_abi_version(void);
 
 #ifdef __cplusplus

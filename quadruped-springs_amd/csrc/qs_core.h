@@ -77,6 +77,7 @@ constexpr float HIP_CYL_HALF_LEN = 0.02f, HIP_CYL_R = 0.046f;                   
 constexpr float LINK_BOX_Z = -0.1065f, THIGH_HALF[3] = {0.017f, 0.01225f, 0.1065f}, CALF_HALF[3] = {0.008f, 0.008f, 0.1065f};
 constexpr float PAYLOAD_I = 0.1f * 0.1f / 6.0f;                                            // cube of half extent 0.05, quadruped.py:793
 constexpr float PAYLOAD_HALF = 0.05f, THR_PAYLOAD = 0.00173f;                              // its box against the plane (0.02 x |half extents|)
+constexpr float SHOULDER_CYL_R = 0.041f, SHOULDER_CYL_HALF_LEN = 0.016f;           // thigh-shoulder cylinder :158-160 (drawn by qs_render only)
 constexpr float HIP_SELF_R = 0.046f;   // link-link tests treat the hip's motor housing (cylinder r 0.046, half length 0.02) as a sphere
 }  // namespace go1
 

@@ -175,7 +175,8 @@ enum { CTL_SETTLE_SUBSTEPS = 0, CTL_RESETS = 1, CTL_SERVED = 2, CTL_SETTLED = 3,
        CTL_R = 8 /* one per cohort */, CTL_TERM_CNT = 8 + QS_COHORTS /* two */, CTL_DEV = 10 + QS_COHORTS /* QS_DEVCTR_*: the rare paths' telemetry */,
        /* (CTL_DEV + 2 .. + 11: the counting builds' counters, qs_core.h, tools/probe_*.py) */
        CTL_PUSH_REFUSED = 22 + QS_COHORTS /* 1 + the first environment whose row qs_set_external_wrench refused, 0 if none */,
-       CTL_N = 23 + QS_COHORTS };
+       CTL_RENDER_REFUSED = 23 + QS_COHORTS /* 1 + the first position of a qs_render call's env_ids that held an id out of range, 0 if none */,
+       CTL_N = 24 + QS_COHORTS };
 
 // settled-state fields a look-ahead reset copies into the record (everything the 2500-substep settle determines), and the slot's tag.
 // Every load is issued before the first value is used: as four rolled loops (`rec[i] = src[i]`) the copy was a load, a wait and an LDS write
@@ -1202,15 +1203,29 @@ int qs_set_external_wrench(qs_handle* h, const uint8_t* mask, const float* wrenc
     return 0;
 }
 
-// after a synchronisation: fails once if qs_set_external_wrench refused a row since the last report
+// after a synchronisation: fails once if qs_set_external_wrench refused a row, or qs_render met an environment id out of range, since the last report
 static int push_refusal(qs_handle* h) {
-    unsigned long long v = 0;
+    unsigned long long v = 0, r = 0;
     QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_PUSH_REFUSED], sizeof(v), hipMemcpyDeviceToHost));
+    QS_HIP(hipMemcpy(&r, &h->d_stats[CTL_RENDER_REFUSED], sizeof(r), hipMemcpyDeviceToHost));
+    if (v == 0 && r != 0) {   // (a push refusal goes first; this one then waits for the next report)
+        QS_HIP(hipMemset(&h->d_stats[CTL_RENDER_REFUSED], 0, sizeof(r)));
+        QS_FAIL(-1, "qs_render got an environment id out of range (%d environments) at position %llu of env_ids (and maybe others): drawn as sky "
+                    "with segmentation id -2", h->cfg.n_envs, r - 1);
+    }
     if (v == 0) return 0;
     QS_HIP(hipMemset(&h->d_stats[CTL_PUSH_REFUSED], 0, sizeof(v)));
     QS_FAIL(-1, "qs_set_external_wrench refused the row of environment %llu (and maybe others): a negative duration or a non-finite force / "
                 "torque; those environments kept their earlier push", v - 1);
 }
+
+}  // extern "C"
+int qs_render_view(qs_handle* h, QsRenderView* v) {
+    v->rec = h->d_rec; v->n_envs = h->cfg.n_envs; v->payload_soft = h->cfg.payload_soft; v->device = h->device;
+    v->stream = h->stream; v->refused = h->d_stats + CTL_RENDER_REFUSED;
+    return 0;
+}
+extern "C" {
 
 int qs_set_trace(qs_handle* h, int env, float* rows) {
     if (!h) QS_FAIL(-1, "null handle");

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the C-ABI translation units (qs_hip.hip, qs_norm.hip).
+// Host-side helpers shared by the C-ABI translation units (qs_hip.hip, qs_norm.hip, qs_render.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,3 +11,13 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 #define QS_ON_DEVICE(h) DeviceGuard qs_guard_((h)->device)
+
+// What qs_render (qs_render.hip) reads of a simulation handle (defined in qs_hip.hip, which owns the handle's layout).
+struct qs_handle;
+struct QsRenderView {
+    const float* rec;              // records [n_envs][QS_REC]
+    int n_envs, payload_soft, device;
+    hipStream_t stream;
+    unsigned long long* refused;   // device counter: 1 + the first position of env_ids that held an id out of range, 0 if none
+};
+int qs_render_view(qs_handle* h, QsRenderView* v);

@@ -4,6 +4,7 @@ import numpy as np
 
 from ..config import EPISODE_LENGTH, scale_command_to_action, to_actual_action_space
 from ..kinematics import leg_fk_jacobian, leg_ik
+from ..render import Camera, render_states
 from ..spaces import GymEnv
 from ..vec_env import QuadrupedVecEnv
 
@@ -307,6 +308,7 @@ class QuadrupedGymEnv(GymEnv):
         # launch of thousands waits for the one wave whose robot has just fallen; with one environment nobody waits.
         solver_settings.setdefault("body_contacts", True)
         self.verbose = verbose
+        self._camera_mode = camera_mode   # checked at the first render() (utils/camera.py): the constructor takes any value
         self._vec = QuadrupedVecEnv(
             num_envs=1, device=device, auto_reset=False, isRLGymInterface=isRLGymInterface, time_step=time_step,
             action_repeat=action_repeat, motor_control_mode=motor_control_mode, task_env=task_env,
@@ -394,7 +396,19 @@ class QuadrupedGymEnv(GymEnv):
         return self._as_dict(obs[0]), float(rew[0]), bool(done[0]), info
 
     def render(self, mode="rgb_array"):
-        return None
+        """gym_env.py:334-335 -> utils/camera.py:35-59: the camera image [1080, 1440, 3] uint8 under the constructor's camera_mode (KeyError
+        for a mode utils/camera.py does not know), np.array([]) for any other mode.  Inside a sub-step callback: the replayed substep."""
+        if mode != "rgb_array":
+            return np.array([])
+        cam = Camera.from_mode(self._camera_mode)
+        if self._replay_row is None:
+            rgb, _, _ = self._vec.render_tensor(camera=cam)   # (the one environment)
+        else:
+            t = self._vec.torch
+            st = t.from_numpy(np.asarray(self._replay_row[1:38], np.float32)[None]).to(self._vec.device)
+            w, h = self._vec.render_size
+            rgb, _, _ = render_states(st, self._vec.get_info("params"), camera=cam, width=w, height=h)
+        return np.ascontiguousarray(rgb[0].cpu().numpy())
 
     def close(self):
         self._vec.close()

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import lib as _lib
 from .config import DEMO_FILES, OBSERVATION_EPS, build_config
+from .render import DEFAULT_SIZE, as_camera, check_request, rgb_view, tile_images
 from .spaces import Box, SB3VecEnv
 
 INFO = dict(foot_force=0, foot_contact=1, torque=2, spring_torque=3, task=4, n_invalid=5, params=6, counters=7,
@@ -74,6 +75,11 @@ class QuadrupedVecEnv(SB3VecEnv):
         self._trace = None
         self._push_keep = None        # the inputs of the last apply_external_force, alive until its kernel has read them
         self.render_mode = None
+        self.render_indices = None        # environments get_images / render draw (None = all, as SB3 renders every sub-environment)
+        self.render_size = DEFAULT_SIZE   # (width, height)
+        self.camera_mode = "CLASSIC"      # qs_amd.render.CAMERA_MODES, or a render.Camera
+        self._render_all = None           # device int32 [0, N) for render_indices = None
+        self._render_keep = None          # the ids of the last render, alive until its kernel has read them
         self.demo_list, self.demo_length = None, 0
         if load_demo and self.meta["task_env"] in DEMO_FILES:
             if self.meta["demo"] is None:
@@ -497,11 +503,64 @@ class QuadrupedVecEnv(SB3VecEnv):
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False] * len(self._indices(indices))
 
-    def get_images(self):
-        return [None] * self.num_envs
+    # ---- camera images (QuadrupedGymEnv.render, utils/camera.py:35-59, for many environments at once; include/qs_amd.h qs_render)
+    def _render_ids(self, indices):
+        """device int32 ids; host ids are checked here and go over through page-locked staging without blocking"""
+        t = self.torch
+        if indices is None:
+            if self._render_all is None:
+                self._render_all = t.arange(self.num_envs, dtype=t.int32, device=self.device)
+            return self._render_all
+        if isinstance(indices, t.Tensor) and indices.device == self.device:
+            if indices.dtype.is_floating_point or indices.dtype == t.bool or indices.dim() != 1:
+                raise ValueError(f"indices must be a 1-D integer tensor, got {indices.dtype} {tuple(indices.shape)}")
+            return indices.to(t.int32).contiguous()   # (not inspected on the host: an id out of range draws sky, id -2, and stats() raises)
+        a = np.asarray(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices))
+        if a.dtype.kind not in "iu" or a.ndim != 1:
+            raise ValueError(f"indices must be integers, got {indices!r}")
+        if a.size and (a.min() < 0 or a.max() >= self.num_envs):
+            raise ValueError(f"environment ids must lie in [0, {self.num_envs}), got {a.min()} .. {a.max()}")
+        h = t.from_numpy(a.astype(np.int32)).pin_memory()
+        return h.to(self.device, non_blocking=True)
 
-    def render(self, mode="rgb_array"):
-        return None
+    def _render(self, indices, camera, width, height, depth, segmentation):
+        t = self.torch
+        cam = as_camera(self.camera_mode if camera is None else camera)
+        w0, h0 = self.render_size
+        width, height = int(w0 if width is None else width), int(h0 if height is None else height)
+        ids = self._render_ids(self.render_indices if indices is None else indices)
+        m = ids.shape[0]
+        check_request(m, width, height, "render_indices or render_size")
+        self._stream()
+        rgba = t.empty((m, height, width), dtype=t.int32, device=self.device)
+        d = t.empty((m, height, width), dtype=t.float32, device=self.device) if depth else None
+        sg = t.empty((m, height, width), dtype=t.int32, device=self.device) if segmentation else None
+        c = cam.to_c()
+        _lib.check(self.lib.qs_render(self.h, self._ptr(ids), m, C.byref(c), width, height, self._ptr(rgba),
+                                      None if d is None else self._ptr(d), None if sg is None else self._ptr(sg)))
+        self._render_keep = ids
+        return rgba, d, sg
+
+    def render_tensor(self, indices=None, camera=None, width=None, height=None, depth=False, segmentation=False):
+        """Camera images of the environments `indices` (None: render_indices; a list, an array or a device tensor of ids), on the device and
+        without waiting for it: (rgb uint8 [M, H, W, 3], a view of the packed RGBA buffer; depth float32 [M, H, W] in metres along the view
+        axis or None; segmentation int32 [M, H, W] or None).  camera: a mode name of qs_amd.render.CAMERA_MODES or a render.Camera (None:
+        camera_mode); width / height default to render_size.  Host ids out of range raise here; ids in a device tensor are not inspected:
+        such an image is sky with segmentation id -2, and the next stats() / counter() raises."""
+        rgba, d, sg = self._render(indices, camera, width, height, depth, segmentation)
+        return rgb_view(rgba), d, sg
+
+    def get_images(self, indices=None):
+        """VecEnv.get_images: one uint8 [H, W, 3] array per environment of render_indices (None = all), camera_mode, render_size"""
+        rgba, _, _ = self._render(indices, None, None, None, False, False)
+        host = rgba.cpu().numpy().view(np.uint8).reshape(*rgba.shape, 4)
+        return [np.ascontiguousarray(host[i, :, :, :3]) for i in range(host.shape[0])]
+
+    def render(self, mode="rgb_array", indices=None):
+        """VecEnv.render: the images of get_images tiled as SB3 tiles them (tile_images); only mode "rgb_array" (no window here)"""
+        if mode != "rgb_array":
+            raise NotImplementedError(f"render mode {mode!r}: only 'rgb_array' (this build has no window)")
+        return tile_images(self.get_images(indices))
 
     def _indices(self, indices):
         if indices is None:
