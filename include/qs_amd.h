@@ -160,6 +160,25 @@ typedef struct qs_config {
 typedef struct qs_handle qs_handle;
 
 int qs_create(const qs_config* cfg, int device, qs_handle** out);
+/* The rack (Quadruped(on_rack=True), quadruped.py:86-96, 474-484): createConstraint(robot, -1, -1, -1, JOINT_FIXED, [0,0,0], [0,0,0],
+ * anchor_pos, childFrameOrientation = anchor_quat) -- the base origin held at anchor_pos with the base frame parallel to anchor_quat (xyzw)
+ * by six rows in the same PGS as the contacts: three on the pivot along the world axes, three on the frames' relative rotation; ERP
+ * cfg.joint_erp, impulse bound 500 N x dt, swept after the joint-limit rows and before the contacts, as the payload block's fixed constraint
+ * (cfg.payload_soft) with the world in the place of the block.  on = 1: every reset spawns the robot at the anchor pose and settles it hung
+ * there (look-ahead reset states included); a handle created with on = 0 (or through qs_create) has no rack.  Refused together with
+ * cfg.payload_soft.  Under the friction pyramid every substep of a wave with a hung robot runs in the full build. */
+typedef struct qs_rack {
+    int32_t on;
+    float anchor_pos[3];
+    float anchor_quat[4];   /* xyzw; normalised by qs_create_ex, which refuses a zero or non-finite one */
+} qs_rack;
+/* qs_create with an optional rack (NULL: none; qs_create(cfg, dev, out) = qs_create_ex(cfg, NULL, dev, out)) */
+int qs_create_ex(const qs_config* cfg, const qs_rack* rack, int device, qs_handle** out);
+/* Releases (hung = 0) or hangs again (hung = 1) the masked environments (mask: device pointer to n_envs bytes, NULL = all) for the rest of
+ * their current episode: a reset always hangs the robot again (so the look-ahead reset states never depend on this call).  Re-hanging
+ * pulls the base back to the anchor at the ERP rate, within the impulse bound.  Stream-ordered, no host synchronisation.  Fails on a handle
+ * without a rack. */
+int qs_set_rack(qs_handle* h, const uint8_t* mask, int hung);
 void qs_destroy(qs_handle* h);
 int qs_set_stream(qs_handle* h, void* hip_stream);
 /* mask: device pointer to n_envs bytes, or NULL for all environments */
@@ -207,6 +226,9 @@ enum {
                             * made ignored the caller's action), timer, end time */
     QS_INFO_EXTERNAL_WRENCH = 14,  /* [N,8]: the push of qs_set_external_wrench: force 3, torque 3 (as set, in their frame), remaining substeps,
                                     * frame */
+    QS_INFO_RACK = 15,  /* [N,8], handles with a rack only: 1 while the robot is hung (0 released), the rack's force 3 and torque 3 on the trunk
+                         * over the last substep (world frame, torque about the pivot; impulses / dt), the distance from the base origin to the
+                         * anchor */
 };
 int qs_info_dim(const qs_handle* h, int which);
 int qs_get_info(qs_handle* h, int which, float* out /*[N, qs_info_dim]*/);
@@ -364,9 +386,9 @@ const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
- * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states.  A binding compares it with the
- * QS_ABI_VERSION of the header it was written against. */
-#define QS_ABI_VERSION 7
+ * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
+ * qs_set_rack, QS_INFO_RACK.  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+#define QS_ABI_VERSION 8
 int qs_abi_version(void);
 
 #ifdef __cplusplus

@@ -274,6 +274,9 @@ template <> struct Rng<LaneEmu> {
 // headline).  (Rounds 2-3 repeated the whole env step with the full build: a rare-path wave paid up to two steps' time.)
 // SOFT (HOT builds): the common-path build ALSO holds the payload block's six rows (cfg.payload_soft), next to the twelve foot rows in
 // solve_and_integrate<.., PAY>; without it a common-path build gives up on every substep of such a handle and the full build does the work.
+// RACK: the builds of a handle with a rack (qs_rack): the same six rows with the world in the block's place (rack_rows), in the common-path
+// build (with SOFT: under the implicit cone; without, it gives up on a substep of a wave with a hung robot) and in the full build.  The
+// other builds hold no line of it.
 // the values a substep works on: one set of types for every build of Sim (an env step may start in the common-path build and go on in
 // the full one, qs_env.h)
 template <class T> struct SimTypes {
@@ -311,7 +314,7 @@ template <class T> struct SimTypes {
 
 #include "qs_rare.h"
 
-template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struct Sim : SimTypes<T> {
+template <class T, bool CONE = false, bool HOT = false, bool SOFT = false, bool RACK = false> struct Sim : SimTypes<T> {
     using V = typename T::V;
     using M = typename T::M;
     using V3v = V3<V>;
@@ -920,6 +923,52 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         c.dv = mk3<V>(qsel(rare_mine, r.dv.x, c.dv.x), qsel(rare_mine, r.dv.y, c.dv.y), qsel(rare_mine, r.dv.z, c.dv.z));
     }
 
+    // ---- the rack (qs_rack, quadruped.py:86-96, 474-484: createConstraint(robot, -1, -1, -1, JOINT_FIXED, ..., childFramePosition = anchor,
+    // childFrameOrientation)): the payload block's six rows (payload_rows) with the static world in the block's place -- pivot on the base
+    // origin against the anchor, the base frame against the anchor's orientation --, so there is no second body: 1 / mass and 1 / inertia
+    // are zero, no lever from a block's centre (rB = 0), the anchor's velocity is zero.  The rows exist for every environment of the wave
+    // (their direction is never zero, so neither is a diagonal) and act only where the robot is hung: rhs x act, and the solvers drop the
+    // impulses of a row whose act is 0.
+    static QS_FN void rack_rows(const qs_config& cfg, const State& s, const Spv& vs, V3v Rx, V3v Ry, V3v Rz, const V* Sm, const V* Ld, const float* blk,
+                                PayRows& q) {
+        const QsDevCfg& dc = reinterpret_cast<const QsDevCfg&>(cfg);
+        const float dt = (float)cfg.dt;
+        const V zero = V(0.0f);
+        const V bx = V(dc.rack_quat[0]), by = V(dc.rack_quat[1]), bz = V(dc.rack_quat[2]), bw = V(dc.rack_quat[3]);
+        V perr[3] = {s.pos.x - dc.rack_pos[0], s.pos.y - dc.rack_pos[1], s.pos.z - dc.rack_pos[2]};   // pivot on the base - anchor
+        // orientation error: rotation vector of q_base q_anchor^-1 (world), small angle (as payload_rows)
+        V ex = s.qw * (-bx) + s.qx * bw + s.qy * (-bz) - s.qz * (-by);
+        V ey = s.qw * (-by) - s.qx * (-bz) + s.qy * bw + s.qz * (-bx);
+        V ez = s.qw * (-bz) + s.qx * (-by) - s.qy * (-bx) + s.qz * bw;
+        V ew = s.qw * bw - s.qx * (-bx) - s.qy * (-by) - s.qz * (-bz);
+        V sg = qsel(qlt(ew, zero), V(-2.0f), V(2.0f));
+        V aerr[3] = {sg * ex, sg * ey, sg * ez};
+        q.act = qflag(qgt(T::ld(blk, RK_HUNG), V(0.5f)));
+        q.mM = zero; q.mI = zero;
+        q.rB = mk3<V>(zero, zero, zero);
+        V3v ab[3] = {Rx, Ry, Rz};                                                                         // R^T e_k
+        const V erp = V(cfg.joint_erp * (1.0f / dt));
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const int c = k % 3;
+            if (k < 3) { q.w[k][0] = zero; q.w[k][1] = zero; q.w[k][2] = zero; q.w[k][3] = ab[c].x; q.w[k][4] = ab[c].y; q.w[k][5] = ab[c].z; }
+            else { q.w[k][0] = ab[c].x; q.w[k][1] = ab[c].y; q.w[k][2] = ab[c].z; q.w[k][3] = zero; q.w[k][4] = zero; q.w[k][5] = zero; }
+            lsolve6<V>(Sm, Ld, q.w[k]);
+            V diag = q.w[k][0] * q.w[k][0];
+#pragma unroll
+            for (int i = 1; i < 6; i++) diag = diag + q.w[k][i] * q.w[k][i];
+            q.diag[k] = diag; q.dinv[k] = qrcp(diag);
+            V rel = k < 3 ? dot(ab[c], vs.l) : dot(ab[c], vs.a);
+            V err = k < 3 ? perr[c] : aerr[c];
+            q.rhs[k] = ((-err) * erp - rel) * q.dinv[k] * q.act;
+        }
+    }
+    // the rack's impulses of the substep into the record (QS_INFO_RACK)
+    static QS_FN void rack_store(float* blk, const PayRows& q) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) T::st(blk, RK_LAM + k, q.lam[k]);
+    }
+
     // An external push on the trunk (qs_set_external_wrench): force F and torque tau at the trunk's centre of mass c (its inertial origin,
     // base frame), in the world frame (rotated into the base frame every substep) or fixed to the trunk.  As a generalized force on the base
     // rows it is Q = [c x F_b + tau_b ; F_b], which H a = Q - C takes as the bias C minus Q: folded into f0, the base's own part of Cb.  The
@@ -944,7 +993,8 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     // `detect`: classify the contacts of the non-foot links, the payload block and the link-link pairs (o.n_invalid).  The reference reads
     // GetContactInfo after the LAST stepSimulation of an env step (task_base.py:137-147 via gym_env.py:241-245), so the callers ask for it
     // there only -- unless cfg.body_contacts, where those links' heights decide in every substep whether they push back.
-    // `blk`: the payload block's state in the record (R_BLOCK) under cfg.payload_soft, nullptr otherwise
+    // `blk`: the payload block's state in the record (R_BLOCK) under cfg.payload_soft, nullptr otherwise; in the RACK builds the rack's slots
+    // there (RK_*)
     // `scratch_row`: this environment's observation row in the wave's staging area (unused between two epilogues): the many-rows solve
     // borrows the sixteen rows of the wave (RareSolver)
     // `last`: the contact classification is READ after this substep (the last one of an env step: gym_env.py:241-245); the link-link tests of
@@ -964,6 +1014,9 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         if (HOT && !SOFT && cfg.payload_soft) return 1;   // this build holds no payload rows
         bool hand_over_next = false;
         const bool soft = (!HOT || SOFT) && cfg.payload_soft && blk != nullptr;
+        // (RACK, wave-uniform) some robot of the wave is hung: the rack's rows are built and solved; a wave of released robots skips them
+        const bool rack = RACK && blk != nullptr && T::any(qgt(T::ld(blk, RK_HUNG), V(0.5f)));
+        if (HOT && !SOFT && rack) return 1;                // (RACK under the friction pyramid) this build holds no rack rows
         Model P;
         {   // opaque copies keep the compiler from hoisting the 24 leg constants out of the substep loop (where they would
             // occupy registers for the whole env step); rebuilding them is ~40 multiplications per substep
@@ -1247,7 +1300,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         Spv vs;  // predicted base velocity in base coordinates
         vs.a = mk3<V>(R[0] * s.vang.x + R[3] * s.vang.y + R[6] * s.vang.z, R[1] * s.vang.x + R[4] * s.vang.y + R[7] * s.vang.z, R[2] * s.vang.x + R[5] * s.vang.y + R[8] * s.vang.z);
         vs.l = mk3<V>(R[0] * s.vlin.x + R[3] * s.vlin.y + R[6] * s.vlin.z, R[1] * s.vlin.x + R[4] * s.vlin.y + R[7] * s.vlin.z, R[2] * s.vlin.x + R[5] * s.vlin.y + R[8] * s.vlin.z);
-        if (soft || T::any(qor(qor(act_m, any_lim), any_extra))) {
+        if (soft || rack || T::any(qor(qor(act_m, any_lim), any_extra))) {
         QS_PHASE(8)
         // ---- constraint rows of this leg: 0 normal, 1 t1 = -y_world, 2 t2 = +x_world ; 3..5 joint limits (rare path)
         Row rows[6];
@@ -1322,6 +1375,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         State s_r = s; Out o_r = o;
         PayRows pay_c, pay_r;   // cfg.payload_soft: the block's six rows (built once: payload_rows also applies gravity to the block) and the two solvers' results for them
         if (!HOT && soft) payload_rows(cfg, Pr, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);
+        if (!HOT && rack) rack_rows(cfg, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);
         QS_PHASE_G(39)
         if (!HOT && T::any(qor(any_lim, any_extra))) {
             Row xr[12];   // this leg's rows: contact point c at 3c .. 3c + 2 (0 = the foot), joint limits at 9 + j
@@ -1474,9 +1528,9 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
                 if (T::any(any_lim)) { QS_LIMIT_ROWS(xr + 9) }
                 QS_PHASE_G(40)
                 V lam12[12], plam[6];
-                if (soft) pay_r = pay_c;   // (the rows; the results in it are overwritten)
-                RareSolver<T, CONE>::solve(cfg, Pr.mu, xr, soft ? &pay_r : nullptr, rare_mine, s.warm * cfg.warmstart * rows[0].act, T::wave_scratch(scratch_row), lam12, plam);
-                integrate_rare(cfg, s_r, o_r, xr, lam12, Sm, Ld, BK, R, soft ? &pay_r : nullptr, plam, active);
+                if (soft || rack) pay_r = pay_c;   // (the rows; the results in it are overwritten)
+                RareSolver<T, CONE>::solve(cfg, Pr.mu, xr, (soft || rack) ? &pay_r : nullptr, rare_mine, s.warm * cfg.warmstart * rows[0].act, T::wave_scratch(scratch_row), lam12, plam);
+                integrate_rare(cfg, s_r, o_r, xr, lam12, Sm, Ld, BK, R, (soft || rack) ? &pay_r : nullptr, plam, active);
 #if defined(QS_PROBE_LAZY) && defined(__HIP_DEVICE_COMPILE__)
                 {   // probe[0] environment-substeps with a support point in range, [1] of them with every such row at zero impulse and no joint
                     // at its stop, [2 + 2 m] environments the rule at margin m would have sent to the many-rows solve, [3 + 2 m] environments in
@@ -1503,11 +1557,13 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         // stop, no link on the floor) keep ITS result -- bit for bit what the common-path build gives them in a wave without such a
         // neighbour; only the environments with rare rows take the many-rows solver's.  (Both solvers run for the whole wave: wave votes
         // must not sit under a divergent branch.)
-        if (SOFT || (!HOT && soft)) {
-            if (HOT) payload_rows(cfg, Pr, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);      // (a handle without the block does not launch this build)
+        if (RACK ? rack : (SOFT || (!HOT && soft))) {
+            if (HOT && !RACK) payload_rows(cfg, Pr, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);      // (a handle without the block does not launch this build)
+            if (HOT && RACK) rack_rows(cfg, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);
             if (cfg.solver_residual_threshold > 0.0f) solve_and_integrate<3, true, true>(cfg, Pr.mu, s, o, rows, Sm, Ld, BK, R, &pay_c);
             else solve_and_integrate<3, false, true>(cfg, Pr.mu, s, o, rows, Sm, Ld, BK, R, &pay_c);
-            if (HOT) payload_integrate(cfg, blk, pay_c);
+            if (HOT && !RACK) payload_integrate(cfg, blk, pay_c);
+            if (HOT && RACK) rack_store(blk, pay_c);
         } else {
             if (cfg.solver_residual_threshold > 0.0f) solve_and_integrate<3, true>(cfg, Pr.mu, s, o, rows, Sm, Ld, BK, R);
             else solve_and_integrate<3, false>(cfg, Pr.mu, s, o, rows, Sm, Ld, BK, R);
@@ -1519,6 +1575,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
             s.vlin = mk3<V>(qsel(rare_mine, s_r.vlin.x, s.vlin.x), qsel(rare_mine, s_r.vlin.y, s.vlin.y), qsel(rare_mine, s_r.vlin.z, s.vlin.z));
             s.warm = qsel(rare_mine, s_r.warm, s.warm); o.foot_force = qsel(rare_mine, o_r.foot_force, o.foot_force);
             if (soft) { keep_rare_payload(pay_c, pay_r, rare_mine); payload_integrate(cfg, blk, pay_c); }
+            if (rack) { keep_rare_payload(pay_c, pay_r, rare_mine); rack_store(blk, pay_c); }
         }
 #undef QS_LIMIT_ROWS
 #undef QS_CONTACT_ROW_AT

@@ -8,10 +8,11 @@ namespace qs {
 QS_FN float i2f(int v) { union { int i; float f; } u; u.i = v; return u.f; }
 QS_FN int f2i(float v) { union { int i; float f; } u; u.f = v; return u.i; }
 
-template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struct Env {
+// RACK: the builds of a handle with a rack (qs_rack, Sim): resets spawn at the anchor and hang the robot
+template <class T, bool CONE = false, bool HOT = false, bool SOFT = false, bool RACK = false> struct Env {
     using V = typename T::V;
     using M = typename T::M;
-    using S = Sim<T, CONE, HOT, SOFT>;
+    using S = Sim<T, CONE, HOT, SOFT, RACK>;
     using V3v = V3<V>;
     static constexpr float PI = 3.14159265358979323846f;
 
@@ -664,7 +665,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         if (!RESUME) { QS_LOAD_COUNTERS }
         const int n_sub = settle_n > 0 ? settle_n : cfg.action_repeat;
         if (settle_n > 0) push = nullptr;   // (a settle never sees a push)
-        float* const blk = cfg.payload_soft ? rec + R_BLOCK : nullptr;
+        float* const blk = (RACK || cfg.payload_soft) ? rec + R_BLOCK : nullptr;
         if (HOT) {
             // what a resumed step needs of the prologue goes into the (still unused) observation row here, once per step and whether or not
             // the step is ever handed over: 30 LDS writes -- stored only at the hand-over, these values stayed live for that cold block all
@@ -874,12 +875,30 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
     // with the sim counter frozen (interface_base.py:182-200), task / sensor / filter reset.
     // First half of reset(): randomizer draws + the spawn state (quadruped.py:454-519), written into the record.  Used by the
     // streaming reset pool, whose settle then proceeds in slices through step(..., settle_n).
+    // the spawn pose (quadruped.py:474-484): INIT_POSITION, or on a rack INIT_RACK_POSITION at the anchor's orientation -- and the robot hung
+    static QS_FN void spawn_pose(const qs_config& cfg, float* rec, typename S::State& s) {
+        const V zero = V(0.0f);
+        if (RACK) {
+            const QsDevCfg& dc = reinterpret_cast<const QsDevCfg&>(cfg);
+            s.pos = mk3<V>(V(dc.rack_pos[0]), V(dc.rack_pos[1]), V(dc.rack_pos[2]));
+            s.qx = V(dc.rack_quat[0]); s.qy = V(dc.rack_quat[1]); s.qz = V(dc.rack_quat[2]); s.qw = V(dc.rack_quat[3]);
+            rack_hang(rec, true);
+        } else {
+            s.pos = mk3<V>(zero, zero, V(0.32f)); s.qx = zero; s.qy = zero; s.qz = zero; s.qw = V(1.0f);
+        }
+    }
+    // (RACK) a reset hangs the robot; `clear`: the rack's impulses start from zero (a settle leaves its last substep's behind)
+    static QS_FN void rack_hang(float* rec, bool clear) {
+        T::st(rec, R_BLOCK + RK_HUNG, V(1.0f));
+        if (clear) for (int k = 0; k < 6; k++) T::st(rec, R_BLOCK + RK_LAM + k, V(0.0f));
+        T::sync();   // (lane 0 wrote what every lane of the quad reads in the substeps)
+    }
     static QS_FN void settle_spawn(const qs_config& cfg, float* rec, uint32_t env_id, int episode) {
         randomize(cfg, rec, env_id, episode, false);
         T::sync();
         typename S::State s; typename S::Out o;
         const V zero = V(0.0f);
-        s.pos = mk3<V>(zero, zero, V(0.32f)); s.qx = zero; s.qy = zero; s.qz = zero; s.qw = V(1.0f);
+        spawn_pose(cfg, rec, s);
         s.vlin = mk3<V>(zero, zero, zero); s.vang = mk3<V>(zero, zero, zero);
         s.q[0] = zero; s.q[1] = V(0.25f * PI); s.q[2] = V(-0.5f * PI);
         s.qd[0] = zero; s.qd[1] = zero; s.qd[2] = zero; s.warm = zero;
@@ -903,7 +922,7 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
         if (settle) {
             randomize(cfg, rec, env_id, episode, false);
             T::sync();  // parameters were written by lane 0 of the quad
-            s.pos = mk3<V>(zero, zero, V(0.32f)); s.qx = zero; s.qy = zero; s.qz = zero; s.qw = V(1.0f);
+            spawn_pose(cfg, rec, s);
             s.vlin = mk3<V>(zero, zero, zero); s.vang = mk3<V>(zero, zero, zero);
             s.q[0] = zero; s.q[1] = V(0.25f * PI); s.q[2] = V(-0.5f * PI);
             s.qd[0] = zero; s.qd[1] = zero; s.qd[2] = zero; s.warm = zero;
@@ -917,10 +936,11 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false> struc
             for (int j = 0; j < 3; j++) cmd[j] = T::ld_leg(cfg.settle_cmd, j, 3);
             for (int n = 0; n < cfg.settle_steps; n++) {
                 V tau[3]; S::actuate(cfg, P, s, cmd, o, tau, true);
-                S::substep(cfg, P, s, tau, o, n == cfg.settle_steps - 1 || cfg.body_contacts, cfg.payload_soft ? rec + R_BLOCK : nullptr, obs, n == cfg.settle_steps - 1);
+                S::substep(cfg, P, s, tau, o, n == cfg.settle_steps - 1 || cfg.body_contacts, (RACK || cfg.payload_soft) ? rec + R_BLOCK : nullptr, obs, n == cfg.settle_steps - 1);
             }
             store_state(rec, s, o);
         } else {  // the record already holds a settled state (copied from the pre-settled pool)
+            if (RACK) rack_hang(rec, false);   // (a look-ahead state was settled hung; reference-state initialisation: the rack pulls the base over)
             load_state(rec, s);
             o.foot_force = T::ld_leg(rec, R_FOOT_FORCE, 1); o.foot_contact = T::ld_leg(rec, R_FOOT_CONTACT, 1); o.n_invalid = T::ld(rec, R_N_INVALID);
 #pragma unroll

@@ -259,7 +259,9 @@ __global__ __launch_bounds__(QS_WAVE, 1) void k_init(const qs_config* __restrict
 // QuadrupedGymEnv.step for 16 environments per wave (gym_env.py:227-256); auto-reset per the SB3 VecEnv convention.
 // The body is compiled twice (k_step / k_step_dense below) under different register budgets.
 // SOFT: the build for handles with cfg.payload_soft whose common-path part holds the payload block's rows (qs_core.h; implicit cone only)
-template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ void step_body(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
+// RACK: the build for handles with a rack (qs_rack; its common-path part holds the rack's rows under the implicit cone, SOFT = CONE): the
+// records' block slots (RK_*) travel with the tile
+template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ __forceinline__ void step_body(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
                                                  const float* __restrict__ actions, float* __restrict__ obs_out,
                                                  float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
                                                  uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep,
@@ -270,12 +272,12 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
     // both kernels: as real functions (round 2) the many-rows solvers took State / Out by reference, which kept them in memory around the
     // call, and expressions that then span a store and a load are no longer contracted into the FMAs the common-path build forms -- a wave
     // on a rare path gave its other 15 environments different last bits (tests/test_gpu_round2.py::test_results_do_not_depend_on_wave_mates).
-    using E = Env<LaneDev, CONE, false>;                // the full build: resets, in-step settle, the rest of a handed-over step
-    using EH = Env<LaneDev, CONE, true, SOFT>;          // the env step: common-path substeps, then (rare) the full build's (qs_env.h, Env::step)
+    using E = Env<LaneDev, CONE, false, false, RACK>;   // the full build: resets, in-step settle, the rest of a handed-over step
+    using EH = Env<LaneDev, CONE, true, SOFT, RACK>;    // the env step: common-path substeps, then (rare) the full build's (qs_env.h, Env::step)
     // LDS (sized at launch, step_lds_bytes): the 16 records at stride `ls`, the observation rows, the action rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     const qs_config& cfg = *cfgp;
-    const int ls = cfg.payload_soft ? (int)QS_REC_END : (int)QS_INFO_END;
+    const int ls = (RACK || cfg.payload_soft) ? (int)QS_REC_END : (int)QS_INFO_END;
     float* const s_rec = s_dyn;
     float* const s_obs = s_dyn + QS_ENVS_PER_WAVE * ls;
     float* const s_act = s_obs + QS_ENVS_PER_WAVE * QS_MAX_OBS;
@@ -312,7 +314,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
         if (push.rows && valid) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
     } else job = lanes.stage_jobs[valid ? env : first];
     const bool spawn = settling && lanes.spawn[cohort], last = settling && lanes.last[cohort];
-    const int load_extent = settling ? (spawn ? 0 : (cfg.payload_soft ? (int)TILE_ALL : (int)QS_SETTLE_END)) : tile_extent(cfg, false);
+    const int load_extent = settling ? (spawn ? 0 : ((RACK || cfg.payload_soft) ? (int)TILE_ALL : (int)QS_SETTLE_END)) : (RACK ? (int)TILE_ALL : tile_extent(cfg, false));
     // (a settle's first slice writes parameters and spawn state itself and reads nothing; its last slice leaves a whole record behind,
     // of which only the settled fields mean anything: the rest is zero rather than whatever the LDS held)
     if (load_extent > 0) tile_load(s_rec, base, first, limit, load_extent, ls);
@@ -356,7 +358,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
         // a slice of a settle changes the rigid-body state and the warm start; its first slice also drew the parameters, its last one
         // leaves the info block's results (and n_invalid) that copy_settled hands to a reset
         tile_store(s_rec, base, first, limit, spawn ? 0 : (int)QS_RW_BEGIN,
-                   cfg.payload_soft ? (int)TILE_ALL : (last ? (int)TILE_INFO : (int)QS_SETTLE_END), ls);
+                   (RACK || cfg.payload_soft) ? (int)TILE_ALL : (last ? (int)TILE_INFO : (int)QS_SETTLE_END), ls);
         return;
     }
     const bool dn = r.done > 0.5f;
@@ -390,7 +392,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
                         quad_row_store(row + 1, ob, od);
                     }
                 }
-                ahead = lookahead_take(la, stats, rec, env, qs::f2i(rec[R_EPISODE]) + 1, cfg.payload_soft != 0);
+                ahead = lookahead_take(la, stats, rec, env, qs::f2i(rec[R_EPISODE]) + 1, RACK || cfg.payload_soft != 0);
             }
             LaneDev::sync();
             if (__builtin_expect(__any(do_reset && !ahead), 0)) {
@@ -400,7 +402,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
                 // k_reset does) and only the resetting environments keep the result -- one whose state was ready gets from its own settle the
                 // very bits it had copied from its slot.
                 __syncthreads();
-                tile_store(s_rec, recs, first, cfg.n_envs, QS_RW_BEGIN, tile_extent(cfg, true), ls);
+                tile_store(s_rec, recs, first, cfg.n_envs, QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls);
                 obs_store(s_obs, min(QS_ENVS_PER_WAVE, cfg.n_envs - first), od, first, obs_out, rew_out == nullptr, obs_keep);
                 __syncthreads();
                 E::reset(cfg, rec, ob, gid, true);
@@ -408,7 +410,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
                 LaneDev::sync();
                 if (do_reset) {
                     float* g = recs + (size_t)env * QS_REC;
-                    const int end = tile_extent(cfg, true);
+                    const int end = RACK ? (int)TILE_ALL : tile_extent(cfg, true);
                     for (int i = threadIdx.x & 3; i < end; i += 4) g[i] = rec[i];
                     for (int i = threadIdx.x & 3; i < od; i += 4) {
                         if (rew_out) obs_out[(size_t)env * od + i] = ob[i];
@@ -422,7 +424,7 @@ template <bool CONE, int WAVES, bool SOFT> static __device__ __forceinline__ voi
         }
     }
     __syncthreads();
-    tile_store(s_rec, recs, first, cfg.n_envs, any_reset ? 0 : (int)QS_RW_BEGIN, tile_extent(cfg, true), ls);
+    tile_store(s_rec, recs, first, cfg.n_envs, any_reset ? 0 : (int)QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls);
     obs_store(s_obs, min(QS_ENVS_PER_WAVE, cfg.n_envs - first), od, first, obs_out, rew_out == nullptr, obs_keep);
     QS_PHASE(15)
 }
@@ -444,6 +446,9 @@ template <bool CONE, bool SOFT> __global__ __launch_bounds__(QS_WAVE, 1) void k_
 // code) -- which measured as NO change of throughput (146.3 against 146.5 M at 16384, round 4): with two waves per SIMD the loop is bound by
 // VALU issue, and the scratch traffic hides behind the other wave.
 template <bool CONE, bool SOFT> __global__ __launch_bounds__(QS_WAVE, 2) void k_step_dense(QS_STEP_ARGS) { step_body<CONE, 2, SOFT>(QS_STEP_PASS); }
+// the same two for handles with a rack (qs_rack)
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_step_rack(QS_STEP_ARGS) { step_body<CONE, 1, CONE, true>(QS_STEP_PASS); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 2) void k_step_dense_rack(QS_STEP_ARGS) { step_body<CONE, 2, CONE, true>(QS_STEP_PASS); }
 
 // Settle lanes, between two settles of a cohort (an epoch = the launches one settle takes): the staging records that finished settling go
 // to the look-ahead slots of their environments (R_EPISODE marks the slot as holding that episode) ...
@@ -522,13 +527,12 @@ __global__ void k_lookahead_requeue(unsigned long long* __restrict__ ctl, LookAh
 
 // QuadrupedGymEnv.reset for the masked environments (gym_env.py:278-297).  An environment whose look-ahead slot holds the coming episode
 // takes it; the others settle side by side.
-template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
+// RACK: k_reset_rack, for handles with a rack (the robot spawns at the anchor and is hung again)
+template <bool CONE, bool RACK> static __device__ __forceinline__ void reset_body(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
                                                       const uint8_t* __restrict__ mask, float* __restrict__ obs_keep,
                                                       unsigned long long* __restrict__ stats, const float* __restrict__ states, LookAhead la,
-                                                      float* __restrict__ push_rows) {
-    using E = Env<LaneDev, CONE>;
-    __shared__ __attribute__((aligned(16))) float s_rec[QS_TILE_FLOATS];
-    __shared__ __attribute__((aligned(16))) float s_obs[QS_ENVS_PER_WAVE * QS_MAX_OBS];
+                                                      float* __restrict__ push_rows, float* s_rec, float* s_obs) {
+    using E = Env<LaneDev, CONE, false, false, RACK>;
     const qs_config& cfg = *cfgp;
     const int first = blockIdx.x * QS_ENVS_PER_WAVE;
     const int slot = threadIdx.x >> 2, env = first + slot;
@@ -543,7 +547,7 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const
     const uint32_t gid = (uint32_t)((valid ? env : 0) + cfg.env_id_offset);
     bool ahead = false;
     if (sel) {
-        if (states == nullptr) ahead = lookahead_take(la, stats, rec, env, qs::f2i(rec[R_EPISODE]) + 1, cfg.payload_soft != 0);
+        if (states == nullptr) ahead = lookahead_take(la, stats, rec, env, qs::f2i(rec[R_EPISODE]) + 1, RACK || cfg.payload_soft != 0);
         else if (la.K > 0 && (threadIdx.x & 3) == 0) la.cur[env] = qs::f2i(rec[R_EPISODE]) + 1;   // (the look-ahead window moves on all the same)
         if ((threadIdx.x & 3) == 0) atomicAdd(&stats[CTL_RESETS], 1ull);
         if ((threadIdx.x & 3) == 0) push_rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM] = 0.0f;   // a reset cancels the environment's push
@@ -555,6 +559,7 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const
             E::randomize(cfg, rec, gid, qs::f2i(rec[R_EPISODE]) + 1, false);
             for (int i = threadIdx.x & 3; i < 37; i += 4) rec[R_POS + i] = states[(size_t)env * 37 + i];
             for (int i = threadIdx.x & 3; i < 4; i += 4) rec[R_WARM + i] = 0.0f;
+            if (RACK) for (int i = threadIdx.x & 3; i < 6; i += 4) rec[R_BLOCK + RK_LAM + i] = 0.0f;
             if ((threadIdx.x & 3) == 0) {
                 for (int i = 0; i < 4; i++) { rec[R_FOOT_FORCE + i] = 0.0f; rec[R_FOOT_CONTACT + i] = 0.0f; }
                 rec[R_N_INVALID] = 0.0f;
@@ -593,12 +598,16 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(const
         for (int i = threadIdx.x & 3; i < od; i += 4) obs_keep[(size_t)env * od + i] = ob[i];
     }
 }
+#define QS_RESET_ARGS const qs_config* __restrict__ cfgp, float* __restrict__ recs, const uint8_t* __restrict__ mask, float* __restrict__ obs_keep, \
+                      unsigned long long* __restrict__ stats, const float* __restrict__ states, LookAhead la, float* __restrict__ push_rows
+#define QS_RESET_PASS cfgp, recs, mask, obs_keep, stats, states, la, push_rows
+#define QS_RESET_LDS __shared__ __attribute__((aligned(16))) float s_rec[QS_TILE_FLOATS]; __shared__ __attribute__((aligned(16))) float s_obs[QS_ENVS_PER_WAVE * QS_MAX_OBS];
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset(QS_RESET_ARGS) { QS_RESET_LDS reset_body<CONE, false>(QS_RESET_PASS, s_rec, s_obs); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_reset_rack(QS_RESET_ARGS) { QS_RESET_LDS reset_body<CONE, true>(QS_RESET_PASS, s_rec, s_obs); }
 
 // The look-ahead slots at qs_create: entry j = the reset of environment j % N to episode j / N (episodes 0 .. K - 1), all side by side.
-template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_fill(const qs_config* __restrict__ cfgp, LookAhead la) {
-    using E = Env<LaneDev, CONE>;
-    __shared__ __attribute__((aligned(16))) float s_rec[QS_TILE_FLOATS];
-    __shared__ __attribute__((aligned(16))) float s_obs[QS_ENVS_PER_WAVE * QS_MAX_OBS];
+template <bool CONE, bool RACK> static __device__ __forceinline__ void lookahead_fill_body(const qs_config* __restrict__ cfgp, LookAhead la, float* s_rec, float* s_obs) {
+    using E = Env<LaneDev, CONE, false, false, RACK>;
     const qs_config& cfg = *cfgp;
     const int slot = threadIdx.x >> 2;
     const long long j = (long long)blockIdx.x * QS_ENVS_PER_WAVE + slot, total = (long long)cfg.n_envs * la.K;
@@ -616,6 +625,9 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_f
         if (episode == la.K - 1 && (threadIdx.x & 3) == 0) { la.handed[env] = la.K - 1; la.cur[env] = -1; }
     }
 }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_fill(const qs_config* __restrict__ cfgp, LookAhead la) { QS_RESET_LDS lookahead_fill_body<CONE, false>(cfgp, la, s_rec, s_obs); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_fill_rack(const qs_config* __restrict__ cfgp, LookAhead la) { QS_RESET_LDS lookahead_fill_body<CONE, true>(cfgp, la, s_rec, s_obs); }
+#undef QS_RESET_LDS
 
 __global__ void k_gather(const float* __restrict__ recs, int n, int off, int dim, float* __restrict__ out, int as_int) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -641,6 +653,27 @@ __global__ void k_task_info(const float* __restrict__ recs, int n, float* __rest
     o[43] = (float)qs::f2i(r[R_SIM_STEP]);
     o[44] = demo ? r[R_DEMO] : 0.0f; o[45] = demo ? r[R_DEMO + 1] : 0.0f;   // demo counter, and at the start of the episode
     for (int k = 46; k < QS_TASK_DIM; k++) o[k] = 0.0f;
+}
+
+// qs_set_rack (and a rack handle's creation): hang or release the masked environments; the rack's impulses start from zero either way
+__global__ void k_set_rack(float* __restrict__ recs, int n, const uint8_t* __restrict__ mask, int hung) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n || (mask && !mask[e])) return;
+    float* b = recs + (size_t)e * QS_REC + R_BLOCK;
+    b[RK_HUNG] = hung ? 1.0f : 0.0f;
+    for (int k = 0; k < 6; k++) b[RK_LAM + k] = 0.0f;
+}
+
+// QS_INFO_RACK: hung, force 3, torque 3 (the six impulses / dt), |base origin - anchor|
+__global__ void k_rack_info(const float* __restrict__ recs, int n, float inv_dt, float ax, float ay, float az, float* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float* r = recs + (size_t)e * QS_REC;
+    float* o = out + (size_t)e * 8;
+    o[0] = r[R_BLOCK + RK_HUNG];
+    for (int k = 0; k < 6; k++) o[1 + k] = r[R_BLOCK + RK_LAM + k] * inv_dt;
+    const float dx = r[R_POS] - ax, dy = r[R_POS + 1] - ay, dz = r[R_POS + 2] - az;
+    o[7] = sqrtf(dx * dx + dy * dy + dz * dz);
 }
 
 #ifdef QS_ISA_ONLY
@@ -677,6 +710,7 @@ struct qs_handle {
     float* trace_rows; int trace_env;
     float* d_demo; int demo_len;   // qs_set_demo
     float* d_push;          // [N][QS_PUSH_F]: qs_set_external_wrench
+    qs_rack rack;           // qs_create_ex: on = 1 -> the rack's kernels (k_step_rack, k_reset_rack, k_lookahead_fill_rack)
     int push_live;          // a push may be pending: the step launches read d_push (cleared by a reset of every environment)
     int n_simd, step_variant;   // SIMDs of the device; 0 = pick k_step / k_step_dense by grid size, 1 / 2 = forced (QS_STEP_VARIANT)
     unsigned long long* d_stats;
@@ -711,10 +745,29 @@ const char* qs_last_error(void) { return g_err; }
 const char* qs_version(void) { return "qs_amd 0.6 (gfx950, quad-per-env; ABI " QS_STR(QS_ABI_VERSION) "; source " QS_SOURCE_SHA ")"; }
 int qs_abi_version(void) { return QS_ABI_VERSION; }
 
-static int create_impl(const qs_config* cfg, int device, qs_handle* h);
+static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs_handle* h);
 
-int qs_create(const qs_config* cfg, int device, qs_handle** out) {
+int qs_create(const qs_config* cfg, int device, qs_handle** out) { return qs_create_ex(cfg, nullptr, device, out); }
+
+int qs_create_ex(const qs_config* cfg, const qs_rack* rack_in, int device, qs_handle** out) {
     if (!cfg || !out) QS_FAIL(-1, "null argument");
+    qs_rack rack;
+    memset(&rack, 0, sizeof(rack));
+    if (rack_in && rack_in->on) {
+        if (rack_in->on != 1) QS_FAIL(-1, "qs_rack::on must be 0 or 1, got %d", rack_in->on);
+        if (cfg->payload_soft)
+            QS_FAIL(-1, "on_rack together with payload_soft is not supported: both are a six-row fixed constraint on the trunk, and the solvers hold "
+                        "one such set; use the welded payload (payload_soft = 0) on a rack");
+        double n2 = 0.0;
+        bool finite = true;
+        auto fin = [](float x) { uint32_t u; memcpy(&u, &x, 4); return (u & 0x7f800000u) != 0x7f800000u; };   // (bits: -ffinite-math-only folds isfinite)
+        for (int i = 0; i < 3; i++) finite = finite && fin(rack_in->anchor_pos[i]);
+        for (int i = 0; i < 4; i++) { finite = finite && fin(rack_in->anchor_quat[i]); n2 += (double)rack_in->anchor_quat[i] * rack_in->anchor_quat[i]; }
+        if (!finite || !(n2 > 1e-12)) QS_FAIL(-1, "the rack's anchor needs a finite position and a finite, non-zero quaternion (xyzw)");
+        rack.on = 1;
+        for (int i = 0; i < 3; i++) rack.anchor_pos[i] = rack_in->anchor_pos[i];
+        for (int i = 0; i < 4; i++) rack.anchor_quat[i] = (float)(rack_in->anchor_quat[i] / sqrt(n2));
+    }
     if (cfg->n_envs <= 0) QS_FAIL(-1, "n_envs must be positive");
     if (cfg->n_envs > (1 << 24)) QS_FAIL(-1, "n_envs %d exceeds %d environments per handle (16 GB of records); shard over more handles", cfg->n_envs, 1 << 24);
     if (cfg->obs_dim <= 0 || cfg->obs_dim > QS_MAX_OBS || cfg->n_sensors > QS_MAX_SENSORS) QS_FAIL(-1, "observation bundle too large");
@@ -747,14 +800,14 @@ int qs_create(const qs_config* cfg, int device, qs_handle** out) {
     qs_handle* h = new (std::nothrow) qs_handle();
     if (!h) QS_FAIL(-4, "out of host memory");
     memset(h, 0, sizeof(*h));
-    int rc = create_impl(cfg, device, h);
+    int rc = create_impl(cfg, &rack, device, h);
     if (rc != 0) { qs_destroy(h); return rc; }   // frees whatever was allocated before the failure (the error text is kept)
     *out = h;
     return 0;
 }
 
-static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
-    h->cfg = *cfg; h->device = device; h->stream = nullptr;
+static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs_handle* h) {
+    h->cfg = *cfg; h->device = device; h->stream = nullptr; h->rack = *rack;
     {
         hipDeviceProp_t prop;
         QS_HIP(hipGetDeviceProperties(&prop, device));
@@ -771,7 +824,10 @@ static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
     QS_HIP(hipMalloc(&h->d_push, n * QS_PUSH_F * sizeof(float)));
     {
         QsDevCfg dc;
+        memset(&dc, 0, sizeof(dc));
         dc.cfg = h->cfg; dc.counters = h->d_stats + CTL_DEV;
+        for (int i = 0; i < 3; i++) dc.rack_pos[i] = h->rack.anchor_pos[i];
+        for (int i = 0; i < 4; i++) dc.rack_quat[i] = h->rack.anchor_quat[i];
         QS_HIP(hipMemcpy(h->d_cfg, &dc, sizeof(dc), hipMemcpyHostToDevice));
     }
     QS_HIP(hipMemset(h->d_obs, 0, n * cfg->obs_dim * sizeof(float)));
@@ -782,6 +838,10 @@ static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
     QS_HIP(hipEventCreate(&h->ev1));
     hipLaunchKernelGGL(k_init, dim3(n_waves(cfg->n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec);
     QS_HIP(hipGetLastError());
+    if (h->rack.on) {   // hung from the start (the first reset spawns at the anchor)
+        hipLaunchKernelGGL(k_set_rack, dim3((cfg->n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_rec, cfg->n_envs, (const uint8_t*)nullptr, 1);
+        QS_HIP(hipGetLastError());
+    }
     // look-ahead reset states: K slots per environment, filled for episodes 0 .. K - 1 before anything steps; not under QS_RAND_KEEP, where
     // a reset's parameters are whatever qs_set_params wrote last (the settle cannot be computed ahead of that)
     memset(&h->la, 0, sizeof(h->la));
@@ -802,7 +862,9 @@ static int create_impl(const qs_config* cfg, int device, qs_handle* h) {
         QS_HIP(hipMemsetAsync(h->d_stage_jobs, 0, (size_t)QS_COHORTS * h->slice * sizeof(int2), h->stream));
 
         const unsigned fill_grid = (unsigned)((n * K + QS_ENVS_PER_WAVE - 1) / QS_ENVS_PER_WAVE);
-        if (cfg->friction_cone) hipLaunchKernelGGL((k_lookahead_fill<true>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
+        if (h->rack.on && cfg->friction_cone) hipLaunchKernelGGL((k_lookahead_fill_rack<true>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
+        else if (h->rack.on) hipLaunchKernelGGL((k_lookahead_fill_rack<false>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
+        else if (cfg->friction_cone) hipLaunchKernelGGL((k_lookahead_fill<true>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
         else hipLaunchKernelGGL((k_lookahead_fill<false>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
         QS_HIP(hipGetLastError());
         h->lanes_on = 1;
@@ -852,11 +914,20 @@ int qs_enable_timing(qs_handle* h, int on) {
     return 0;
 }
 
+static void launch_reset(qs_handle* h, const uint8_t* mask, const float* states) {
+#define QS_LAUNCH_RESET(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, \
+                                                   h->d_stats, states, h->la, h->d_push)
+    if (h->rack.on && h->cfg.friction_cone) QS_LAUNCH_RESET(k_reset_rack<true>);
+    else if (h->rack.on) QS_LAUNCH_RESET(k_reset_rack<false>);
+    else if (h->cfg.friction_cone) QS_LAUNCH_RESET(k_reset<true>);
+    else QS_LAUNCH_RESET(k_reset<false>);
+#undef QS_LAUNCH_RESET
+}
+
 int qs_reset(qs_handle* h, const uint8_t* mask) {
     if (!h) QS_FAIL(-1, "null handle");
     QS_ON_DEVICE(h);
-    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la, h->d_push);
-    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, (const float*)nullptr, h->la, h->d_push);
+    launch_reset(h, mask, nullptr);
     QS_HIP(hipGetLastError());
     if (!mask) h->push_live = 0;   // every push is cancelled
     return 0;
@@ -865,8 +936,7 @@ int qs_reset(qs_handle* h, const uint8_t* mask) {
 int qs_reset_to(qs_handle* h, const uint8_t* mask, const float* states) {
     if (!h || !states) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    if (h->cfg.friction_cone) hipLaunchKernelGGL((k_reset<true>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la, h->d_push);
-    else hipLaunchKernelGGL((k_reset<false>), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la, h->d_push);
+    launch_reset(h, mask, states);
     QS_HIP(hipGetLastError());
     if (!mask) h->push_live = 0;
     return 0;
@@ -954,13 +1024,17 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     // more waves than SIMDs: the two-waves-per-SIMD build of the same body (see k_step_dense) instead of a second round of one-wave-per-
     // SIMD workgroups (N = 12288 with its settle lanes: 0.109 ms in two rounds)
     const bool dense = h->step_variant == 2 || (h->step_variant == 0 && (lanes.n_env_waves > h->n_simd || !lanes_fit));
-    const size_t lds = (size_t)QS_ENVS_PER_WAVE * ((h->cfg.payload_soft ? QS_REC_END : QS_INFO_END) + QS_MAX_OBS + 12) * sizeof(float);
+    const size_t lds = (size_t)QS_ENVS_PER_WAVE * (((h->cfg.payload_soft || h->rack.on) ? QS_REC_END : QS_INFO_END) + QS_MAX_OBS + 12) * sizeof(float);
 #define QS_LAUNCH_STEP(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(QS_WAVE), lds, h->stream, h->d_cfg, h->d_rec, actions, obs, rew, done, trunc, \
                                                  h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push)
 #define QS_PICK(C, S) { if (dense) QS_LAUNCH_STEP((k_step_dense<C, S>)); else QS_LAUNCH_STEP((k_step<C, S>)); }
-    if (h->cfg.friction_cone && h->cfg.payload_soft) QS_PICK(true, true)
+#define QS_PICK_RACK(C) { if (dense) QS_LAUNCH_STEP((k_step_dense_rack<C>)); else QS_LAUNCH_STEP((k_step_rack<C>)); }
+    if (h->rack.on && h->cfg.friction_cone) QS_PICK_RACK(true)
+    else if (h->rack.on) QS_PICK_RACK(false)
+    else if (h->cfg.friction_cone && h->cfg.payload_soft) QS_PICK(true, true)
     else if (h->cfg.friction_cone) QS_PICK(true, false)
     else QS_PICK(false, false)
+#undef QS_PICK_RACK
 #undef QS_PICK
 #undef QS_LAUNCH_STEP
     QS_HIP(hipGetLastError());
@@ -1203,6 +1277,16 @@ int qs_set_external_wrench(qs_handle* h, const uint8_t* mask, const float* wrenc
     return 0;
 }
 
+int qs_set_rack(qs_handle* h, const uint8_t* mask, int hung) {
+    if (!h) QS_FAIL(-1, "null handle");
+    if (!h->rack.on) QS_FAIL(-1, "this handle was created without a rack (qs_create_ex with qs_rack::on = 1)");
+    if (hung != 0 && hung != 1) QS_FAIL(-1, "hung must be 0 (release) or 1 (hang), got %d", hung);
+    QS_ON_DEVICE(h);
+    hipLaunchKernelGGL(k_set_rack, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_rec, h->cfg.n_envs, mask, hung);
+    QS_HIP(hipGetLastError());
+    return 0;
+}
+
 // after a synchronisation: fails once if qs_set_external_wrench refused a row, or qs_render met an environment id out of range, since the last report
 static int push_refusal(qs_handle* h) {
     unsigned long long v = 0, r = 0;
@@ -1359,6 +1443,7 @@ int qs_info_dim(const qs_handle* h, int which) {
     case QS_INFO_REWARD_END: return 1;
     case QS_INFO_PAYLOAD_BLOCK: return QS_BLOCK_DIM;
     case QS_INFO_EXTERNAL_WRENCH: return QS_PUSH_F;
+    case QS_INFO_RACK: return 8;
     default: return -1;
     }
 }
@@ -1392,6 +1477,12 @@ int qs_get_info(qs_handle* h, int which, float* out) {
         return 0;
     case QS_INFO_EXTERNAL_WRENCH:
         QS_HIP(hipMemcpyAsync(out, h->d_push, (size_t)h->cfg.n_envs * QS_PUSH_F * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        return 0;
+    case QS_INFO_RACK:
+        if (!h->rack.on) QS_FAIL(-1, "this handle was created without a rack (qs_create_ex with qs_rack::on = 1)");
+        hipLaunchKernelGGL(k_rack_info, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0, h->stream, h->d_rec, h->cfg.n_envs, (float)(1.0 / h->cfg.dt),
+                           h->rack.anchor_pos[0], h->rack.anchor_pos[1], h->rack.anchor_pos[2], out);
+        QS_HIP(hipGetLastError());
         return 0;
     case QS_INFO_TERMINAL_OBS:
         QS_HIP(hipMemcpyAsync(out, h->d_term_obs, (size_t)h->cfg.n_envs * h->cfg.obs_dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));

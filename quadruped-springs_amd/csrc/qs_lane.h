@@ -84,10 +84,11 @@ QS_FN bool qor(bool a, bool b) { return a || b; }
 QS_FN bool qnot(bool a) { return !a; }
 QS_FN float qflag(bool m) { return m ? 1.0f : 0.0f; }
 
-#if defined(__HIPCC__)
 // The configuration as the kernels see it: the public struct, and behind it the handle's counter block -- telemetry of the rare paths
-// (per HANDLE since round 4; a process-wide pair of __device__ variables before: two handles on one GPU mixed their counts).
-struct QsDevCfg { qs_config cfg; unsigned long long* counters; };
+// (per HANDLE since round 4; a process-wide pair of __device__ variables before: two handles on one GPU mixed their counts) -- and the rack's
+// anchor (qs_rack: read by the RACK builds only, qs_core.h; the host emulation passes the same struct)
+struct QsDevCfg { qs_config cfg; unsigned long long* counters; float rack_pos[3]; float rack_quat[4]; };
+#if defined(__HIPCC__)
 enum { QS_DEVCTR_RARE_PATH = 0, QS_DEVCTR_SELF_NARROW = 1 };   // wave-substeps through the many-rows solve / whose broad phase asked for the link-link tests
 struct LaneDev {
     using V = float;

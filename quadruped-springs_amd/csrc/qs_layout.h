@@ -52,6 +52,9 @@ enum {
                           //   and action rows = 20480 B per workgroup, eight workgroups per CU for the two-waves-per-SIMD kernel
 };
 enum { B_POS = 0, B_QUAT = 3, B_V = 7, B_W = 10, B_LAM = 13, B_GAP = 19, QS_BLOCK_DIM = 20 };
+// the same 20 floats on a handle with a rack (qs_rack; refused together with cfg.payload_soft): 1 while the robot is hung, the six impulses
+// of the rack's rows at the last substep.  Moved by the tile load / store of the rack's kernels.
+enum { RK_HUNG = 0, RK_LAM = B_LAM };
 enum { P_MU = 0, P_K = 1, P_B = 4, P_REST = 7, P_KP = 10, P_KD = 13, P_M_TRUNK = 16, P_M_LEG = 17, P_M_PAY = 20, P_R_PAY = 21 };
 enum { T_SWITCHED = 0, T_ALL_AIR = 1, T_IS_JUMPING = 2, T_TAKEOFF = 3, T_POSE_TO = 4, T_YAW_TO = 7, T_INIT_H = 8, T_MAX_FLIGHT = 9,
        T_MAX_FWD = 10, T_MAX_PITCH = 11, T_REL_MAX_H = 12, T_MAX_DX = 13, T_MAX_H = 14, T_CUM_FWD = 15, T_CUM_FT = 16,

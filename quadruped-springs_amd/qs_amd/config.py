@@ -302,9 +302,16 @@ def build_config(
 
     The keywords are the reference constructor's (quadruped_gym_env.py:52-70) plus this build's own; anything else is a TypeError, as it
     is there (a misspelt `enable_spring=True` must not silently simulate without springs).  Of the reference's, `camera_mode`,
-    `curriculum_level` and `verbose` are accepted and unused (rendering / dead curriculum code), `on_rack` and `render` must be False."""
-    if on_rack or render:
-        raise NotImplementedError("on_rack / render need the PyBullet GUI path, which this build does not provide")
+    `curriculum_level` and `verbose` are accepted and unused (rendering / dead curriculum code), `render` must be False (there is no window:
+    render(mode="rgb_array") draws images without it).  on_rack=True hangs the trunk from the world at the robot config's INIT_RACK_POSITION
+    and INIT_ORIENTATION (quadruped.py:86-96, 474-484): meta["rack"] holds what the handle is created with (include/qs_amd.h qs_rack); it is
+    refused together with payload="soft"."""
+    if render:
+        raise NotImplementedError("render=True opens the PyBullet GUI window, which this build does not provide (render(mode='rgb_array') "
+                                  "draws camera images without it)")
+    if on_rack and payload == "soft":
+        raise NotImplementedError("on_rack=True together with payload='soft' is not supported: both are a six-row fixed constraint on the trunk "
+                                  "and the solvers hold one such set; use payload='weld' on a rack")
     if motor_control_mode == "TORQUE" and isRLGymInterface:
         # gym_env.py:167-168
         raise ValueError(f"the motor control mode {motor_control_mode} not" "implemented yet for RL Gym interface.")
@@ -449,7 +456,9 @@ def build_config(
                 init_pose=np.array(init_pose, float), landing_pose=np.array(landing_pose, float),
                 settle_action=np.array(settle_action, float), landing_action=np.array(landing_action, float),
                 action_space_mode=action_space_mode, motor_control_mode=motor_control_mode, task_env=task_env,
-                observation_space_mode=observation_space_mode, env_randomizer_mode=env_randomizer_mode, demo=None)
+                observation_space_mode=observation_space_mode, env_randomizer_mode=env_randomizer_mode, demo=None,
+                rack=dict(on=bool(on_rack), pos=np.array(getattr(rc, "INIT_RACK_POSITION", [0, 0, 1]), np.float32),
+                          quat=np.array(rc.INIT_ORIENTATION, np.float32)))
     if task_env in DEMO_FILES:
         if action_space_mode == "CPG" or not isRLGymInterface:
             raise ValueError("the DEMO tasks compare the policy's action with a recorded one: they need an RL action space")

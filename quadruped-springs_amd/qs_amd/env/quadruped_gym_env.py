@@ -149,6 +149,13 @@ class _RobotView:
     def set_spring_damping(self, b):
         self._env._vec.set_params("spring_b", np.asarray(b, np.float32)[None])
 
+    def _GetDefaultInitPosition(self):                     # quadruped.py:86-96
+        rc = self._robot_config
+        return rc.INIT_RACK_POSITION if self._env._on_rack else rc.INIT_POSITION
+
+    def _GetDefaultInitOrientation(self):                  # quadruped.py:98-105
+        return self._robot_config.INIT_ORIENTATION
+
     def apply_external_force(self, force):                 # quadruped.py:338-343
         """Apply an external force on the quadruped COM: pybullet's applyExternalForce on the trunk at its centre of mass in LINK_FRAME,
         which pybullet clears after the next stepSimulation -- a push of one physics substep, in the trunk's frame."""
@@ -297,8 +304,9 @@ class QuadrupedGymEnv(GymEnv):
         demo=None,    # DEMO tasks: the demonstration rows (array or .npy path) the reference would np.load (task_base.py:173)
         **solver_settings,   # the engine settings of qs_amd.config.build_config (friction_model, contact_erp, body_contacts, payload, ...)
     ):
-        if on_rack or render:
-            raise NotImplementedError("on_rack / render need the PyBullet GUI path, which this build does not provide")
+        if render:
+            raise NotImplementedError("render=True opens the PyBullet GUI window, which this build does not provide (render(mode='rgb_array') "
+                                      "draws camera images without it)")
         unknown = set(solver_settings) - {"friction_model", "contact_erp", "contact_slop", "joint_erp", "warmstart", "solver_residual_threshold",
                                           "body_contacts", "self_collision", "payload", "mass_inertia_rule"}
         if unknown:
@@ -314,8 +322,9 @@ class QuadrupedGymEnv(GymEnv):
             action_repeat=action_repeat, motor_control_mode=motor_control_mode, task_env=task_env,
             observation_space_mode=observation_space_mode, action_space_mode=action_space_mode, enable_springs=enable_springs,
             enable_action_interpolation=enable_action_interpolation, enable_action_filter=enable_action_filter,
-            env_randomizer_mode=env_randomizer_mode, seed=seed, noise=noise, demo=demo, **solver_settings)
+            env_randomizer_mode=env_randomizer_mode, seed=seed, noise=noise, demo=demo, on_rack=on_rack, **solver_settings)
         meta = self._vec.meta
+        self._on_rack = bool(on_rack)
         self._robot_config = meta["robot_config"]
         self._enable_springs = enable_springs
         self._isRLGymInterface = isRLGymInterface
@@ -466,7 +475,11 @@ class QuadrupedGymEnv(GymEnv):
     def get_quadruped_config(self):
         """gym_env.py:395-397: the keyword set the reference builds its Quadruped with (no Bullet client here)."""
         return dict(pybullet_client=None, robot_config=self._robot_config, motor_control_mode="PD" if self._motor_control_mode != "TORQUE" else "TORQUE",
-                    on_rack=False, render=False, enable_springs=self._enable_springs, desired_state=self.robot_desired_state)
+                    on_rack=self._on_rack, render=False, enable_springs=self._enable_springs, desired_state=self.robot_desired_state)
+
+    def set_rack(self, hung):
+        """on_rack=True: release the robot from the rack (hung=False) or hang it again for the rest of the episode; reset() hangs it again."""
+        self._vec.set_rack(hung)
 
     def reinit_randomizers(self, env):
         """gym_env.py:411-413 re-points the Python randomizers at a wrapping env; the randomizers live in the reset kernel here."""

@@ -23,6 +23,7 @@ def make_config(enable_springs: bool) -> SimpleNamespace:
     c = SimpleNamespace()
     c.NUM_MOTORS, c.NUM_LEGS, c.MOTORS_PER_LEG = 12, 4, 3
     c.INIT_POSITION = [0, 0, 0.32]                                   # :23
+    c.INIT_RACK_POSITION = [0, 0, 1]                                 # :22
     c.IS_FALLEN_HEIGHT = 0.10 if enable_springs else 0.12            # :24 / [w/o] :24
     c.INIT_ORIENTATION = (0, 0, 0, 1)                                # :26
     thigh0, calf0 = math.pi / 4, -math.pi / 2                        # :31-33

@@ -9,12 +9,12 @@ from .config import QsConfig
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QS_LIB_PATH") or os.path.join(_HERE, "libqs_hip.so")   # QS_LIB_PATH: kernel experiments (another build of the same ABI)
 
-ABI_VERSION = 7   # QS_ABI_VERSION of include/qs_amd.h this file was written against
+ABI_VERSION = 8   # QS_ABI_VERSION of include/qs_amd.h this file was written against
 
 EXPORTS = (
     "qs_create", "qs_destroy", "qs_set_stream", "qs_reset", "qs_reset_to", "qs_get_obs", "qs_step", "qs_step_fused", "qs_get_state", "qs_set_state",
     "qs_info_dim", "qs_get_info", "qs_set_params", "qs_stats", "qs_enable_timing", "qs_last_step_kernel_ms",
-    "qs_settle_lanes", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
+    "qs_settle_lanes", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_create_ex", "qs_set_rack", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
     "qs_norm_create", "qs_norm_destroy", "qs_norm_dims", "qs_norm_set_stream", "qs_norm_set_stats", "qs_norm_get_stats", "qs_norm_reset", "qs_norm_step",
     "qs_norm_step_io", "qs_host_set_norm",
 )
@@ -39,6 +39,11 @@ class QsCamera(C.Structure):
     """qs_camera (include/qs_amd.h): a camera of qs_render / qs_render_states."""
     _fields_ = [("target", C.c_float * 3), ("distance", C.c_float), ("yaw_deg", C.c_float), ("pitch_deg", C.c_float), ("fov_deg", C.c_float),
                 ("near_clip", C.c_float), ("far_clip", C.c_float), ("follow_base", C.c_int32), ("draw_payload", C.c_int32)]
+
+
+class QsRack(C.Structure):
+    """qs_rack (include/qs_amd.h): the rack of qs_create_ex (Quadruped(on_rack=True))."""
+    _fields_ = [("on", C.c_int32), ("anchor_pos", C.c_float * 3), ("anchor_quat", C.c_float * 4)]
 
 
 _lib = None
@@ -83,6 +88,9 @@ def load():
     lib.qs_set_demo_counter.argtypes = [vp, vp, vp]
     if hasattr(lib, "qs_set_external_wrench"):   # (ABI 6; an older library under QS_ALLOW_ABI_MISMATCH lacks it)
         lib.qs_set_external_wrench.argtypes = [vp, vp, vp, vp, i32]
+    if hasattr(lib, "qs_create_ex"):   # (ABI 8)
+        lib.qs_create_ex.argtypes = [C.POINTER(QsConfig), C.POINTER(QsRack), i32, C.POINTER(vp)]
+        lib.qs_set_rack.argtypes = [vp, vp, i32]
     if hasattr(lib, "qs_render"):   # (ABI 7)
         lib.qs_render.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp]
         lib.qs_render_states.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp, vp]

@@ -14,7 +14,7 @@ from .render import DEFAULT_SIZE, as_camera, check_request, rgb_view, tile_image
 from .spaces import Box, SB3VecEnv
 
 INFO = dict(foot_force=0, foot_contact=1, torque=2, spring_torque=3, task=4, n_invalid=5, params=6, counters=7,
-            last_action=8, terminal_obs=9, wrapper=10, filtered_action=11, reward_end=12, payload_block=13, external_wrench=14)
+            last_action=8, terminal_obs=9, wrapper=10, filtered_action=11, reward_end=12, payload_block=13, external_wrench=14, rack=15)
 PHASE = ("policy", "take_off", "landing", "rest")
 PARAM = dict(mu=0, spring_k=1, spring_b=2, kp=3, kd=4, all=5)
 FRAME = dict(link=1, world=2)   # QS_FRAME_LINK / QS_FRAME_WORLD = pybullet.LINK_FRAME / WORLD_FRAME
@@ -61,7 +61,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         self._init_vec_env_base()
         self.h = C.c_void_p()
         self._closed = False
-        _lib.check(self.lib.qs_create(C.byref(self.cfg), device, C.byref(self.h)))
+        self._create(device)
         n, o = self.num_envs, self.obs_dim
         with torch.cuda.device(self.device):
             self._obs = torch.zeros((n, o), dtype=torch.float32, device=self.device)
@@ -87,6 +87,35 @@ class QuadrupedVecEnv(SB3VecEnv):
                 raise ValueError(f"task {self.meta['task_env']} imitates a demonstration: pass demo=<array [L, action_dim + 38] or path of the "
                                  f".npy> (the reference loads demonstrations/{DEMO_FILES[self.meta['task_env']]}, task_base.py:173)")
             self.set_demo(self.meta["demo"])
+
+    def _create(self, device):
+        """the device handle, with the rack of meta["rack"] when on_rack=True (qs_create_ex)"""
+        rk = self.meta.get("rack")
+        self.on_rack = bool(rk and rk["on"])
+        if self.on_rack:
+            r = _lib.QsRack()
+            r.on = 1
+            for i in range(3):
+                r.anchor_pos[i] = float(rk["pos"][i])
+            for i in range(4):
+                r.anchor_quat[i] = float(rk["quat"][i])
+            _lib.check(self.lib.qs_create_ex(C.byref(self.cfg), C.byref(r), device, C.byref(self.h)))
+        else:
+            _lib.check(self.lib.qs_create(C.byref(self.cfg), device, C.byref(self.h)))
+
+    def set_rack(self, hung, indices=None):
+        """Release (hung=False) or hang again (hung=True) the robots of `indices` (None = all) for the rest of their current episode: a
+        reset hangs every robot again (on_rack=True handles only).  Never waits for the device."""
+        if not self.on_rack:
+            raise RuntimeError("set_rack needs a handle created with on_rack=True")
+        mask = None
+        if indices is not None:
+            m = np.zeros(self.num_envs, np.uint8)
+            m[np.asarray(self._indices(indices), np.int64)] = 1
+            mask = self.torch.from_numpy(m).pin_memory().to(self.device, non_blocking=True)
+            self._rack_keep = mask
+        self._stream()
+        _lib.check(self.lib.qs_set_rack(self.h, None if mask is None else self._ptr(mask), 1 if hung else 0))
 
     def _init_vec_env_base(self):
         """stable_baselines3.common.vec_env.VecEnv.__init__(num_envs, observation_space, action_space) when SB3 is importable and this
@@ -485,7 +514,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         self.cfg.seed = seed
         self._views, self._dirty = {}, []
         self._infos = [{} for _ in range(self.num_envs)]
-        _lib.check(self.lib.qs_create(C.byref(self.cfg), self.device.index or 0, C.byref(self.h)))
+        self._create(self.device.index or 0)
         if self.demo_list is not None:
             self.set_demo(self.demo_list)
         self._trace = None

@@ -1,0 +1,258 @@
+"""The rack (on_rack=True) on the device: the step of hung, released and re-hung robots with either step kernel, bit for bit, and against
+the host emulation, released wave-mates leave the hung ones' bits alone, a released robot's fall against the oracle, look-ahead resets against
+in-place ones, auto-reset and seed() hang the robot again, the single-environment drop-in, and set_rack never waits for the device."""
+import numpy as np
+import pytest
+
+from test_gpu_round2 import RAW, vec_env
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    return torch
+
+
+def bits(x):
+    x = np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x)
+    return x.view(np.int32) if x.dtype == np.float32 else x
+
+
+def same(a, b, what):
+    assert np.array_equal(bits(a), bits(b)), f"{what}: {np.argwhere(bits(a) != bits(b))[:8].tolist()}"
+
+
+def stop_actions(rng, n, d, t):
+    act = rng.uniform(-1, 1, (n, d)).astype(np.float32) * 0.3
+    act[: n // 2, 2::3] = -30.0 if t % 8 < 4 else 30.0   # (raw torques, N m) calves against their stops, one way then the other
+    return act
+
+
+@pytest.mark.parametrize("friction", ["cone", "pyramid"])
+def test_both_step_kernels_agree_and_follow_the_emulation(torch_cuda, monkeypatch, friction):
+    """k_step_rack and k_step_dense_rack bit for bit, and the host emulation's RACK build (its 1 / x and square roots are the exact ones,
+    the device's are v_rcp_f32 / v_sqrt_f32: close, not equal): hung robots with joints at their stops, some released at step 4, all hung
+    again at step 9 (two waves: 20 environments)"""
+    from emu.emu import Emu
+    from emu.emu_rack import rack_info, reset_rack, set_rack, step_rack
+    n = 20
+    kw = dict(on_rack=True, action_repeat=10, settle_steps=300, body_contacts=True, friction_model=friction, env_randomizer_mode="GROUND_RANDOMIZER",
+              reset_lookahead=0, **RAW)
+    vs = []
+    for variant in ("1", "2"):
+        monkeypatch.setenv("QS_STEP_VARIANT", variant)
+        v = vec_env(n, **kw)
+        v.cfg.tau_max[:] = [40.0, 40.0, 40.0]
+        v.seed(int(v.cfg.seed))                  # (a handle with the edited configuration: seed() recreates it, keeping the rack)
+        vs.append(v)
+    e = Emu(vs[0].cfg)
+    for v in vs:
+        v.reset_tensor()
+    reset_rack(e)
+    same(vs[0].get_state(), vs[1].get_state(), "state after the reset")
+    np.testing.assert_allclose(vs[0].get_state().cpu().numpy(), e.get_state(), atol=1e-5)
+    rng = np.random.default_rng(3)
+    t = torch_cuda
+    for k in range(12):
+        if k == 4:
+            m = (np.arange(n) % 3 == 0)
+            for v in vs:
+                v.set_rack(False, indices=np.nonzero(m)[0].tolist())
+            set_rack(e, False, m)
+        if k == 9:
+            for v in vs:
+                v.set_rack(True)
+            set_rack(e, True)
+        a = stop_actions(rng, n, vs[0].action_dim, k)
+        for v in vs:
+            v.step_tensor(t.from_numpy(a).to(v.device))
+        step_rack(e, a, 0)
+        same(vs[0].get_state(), vs[1].get_state(), f"state, step {k}")
+        same(vs[0].get_info("rack"), vs[1].get_info("rack"), f"rack info, step {k}")
+        dev, emu = vs[0].get_state().cpu().numpy(), e.get_state()
+        np.testing.assert_allclose(dev[:, :13], emu[:, :13], atol=2e-3, err_msg=f"base state, step {k}")
+        np.testing.assert_array_equal(vs[0].get_info("rack").cpu().numpy()[:, 0], rack_info(e)[:, 0])
+
+
+@pytest.mark.parametrize("step_kernel", ["1", "2"])
+def test_released_and_hung_wave_mates_leave_each_other_alone(torch_cuda, monkeypatch, step_kernel):
+    """three handles: every robot hung (a), four released among hung wave-mates (b), every robot released (c).  The hung robots of b keep the
+    bits of a's; the released robots of b -- whose waves build and sweep the rack's rows with act = 0 -- have the values of c's, whose waves
+    skip the rows, through the fall and the landing (equal as numbers: only the sign of a zero may tell the two paths apart)"""
+    monkeypatch.setenv("QS_STEP_VARIANT", step_kernel)
+    n = 32
+    a = vec_env(n, on_rack=True, reset_lookahead=0)
+    b = vec_env(n, on_rack=True, reset_lookahead=0)
+    c = vec_env(n, on_rack=True, reset_lookahead=0)
+    a.reset_tensor(); b.reset_tensor(); c.reset_tensor()
+    rel = [3, 7, 16, 30]
+    b.set_rack(False, indices=rel)
+    c.set_rack(False)
+    rng = np.random.default_rng(0)
+    t = torch_cuda
+    hung = np.setdiff1d(np.arange(n), rel)
+    for k in range(70):
+        act = t.from_numpy(rng.uniform(-1, 1, (n, a.action_dim)).astype(np.float32)).to(a.device)
+        a.step_tensor(act); b.step_tensor(act); c.step_tensor(act)
+        sb = b.get_state()
+        same(a.get_state()[hung], sb[hung], f"hung robots, step {k}")
+        np.testing.assert_array_equal(sb[rel].cpu().numpy(), c.get_state()[rel].cpu().numpy(), err_msg=f"released robots, step {k}")
+        np.testing.assert_array_equal(b.get_info("rack")[rel].cpu().numpy(), c.get_info("rack")[rel].cpu().numpy())
+    assert (b.get_state()[rel, 2] < 0.5).all() and (a.get_state()[:, 2] > 0.99).all()   # (the released ones are down on the floor)
+
+
+def test_released_robot_falls_as_the_oracle(torch_cuda):
+    """the released robot is an ordinary robot: its fall under raw joint torques (before touchdown) follows the unchanged float64 oracle
+    from the state it was released in"""
+    from oracle.qso import Oracle
+    n = 16
+    v = vec_env(n, on_rack=True, reset_lookahead=0, **RAW)
+    o = Oracle(v.cfg)
+    v.reset_tensor()
+    v.set_rack(False)
+    o.set_state(v.get_state().cpu().numpy().astype(np.float64))
+    rng = np.random.default_rng(1)
+    for k in range(25):
+        act = rng.uniform(-2, 2, (n, v.action_dim)).astype(np.float32)
+        o.step(act)
+        v.step(act)
+        sv, so = v.get_state().cpu().numpy(), o.get_state()
+        assert np.abs(sv[:, :13] - so[:, :13]).max() < 1e-3, (k, np.abs(sv[:, :13] - so[:, :13]).max())
+        assert np.abs(sv[:, 13:] - so[:, 13:]).max() < 1e-2, (k, np.abs(sv[:, 13:] - so[:, 13:]).max())
+    assert (v.get_state().cpu().numpy()[:, 2] < 0.8).all()
+
+
+def test_lookahead_resets_equal_in_place_resets(torch_cuda):
+    n = 24
+    a = vec_env(n, on_rack=True, reset_lookahead=0)
+    b = vec_env(n, on_rack=True, reset_lookahead=4)
+    for k in range(3):
+        a.reset_tensor(); b.reset_tensor()
+        same(a.get_state(), b.get_state(), f"state after reset {k}")
+        same(a.get_info("rack"), b.get_info("rack"), f"rack info after reset {k}")
+
+
+@pytest.mark.parametrize("step_kernel", ["1", "2"])
+def test_settle_lanes_and_auto_resets_equal_in_place_resets(torch_cuda, monkeypatch, step_kernel):
+    """an auto-reset rack handle with look-ahead states (K = 2) against the same run with every reset settled in place (K = 0), bit for bit
+    after every step: the states of qs_create, the settle lanes' (spawn slice at the anchor, hung settle slices through the step kernel's
+    substep loop, published to the slots), the in-step resets that take them, and in-step settles where a state was not ready yet, next to
+    taken ones in the same wave.  Episodes end by released robots put below the fallen height."""
+    monkeypatch.setenv("QS_STEP_VARIANT", step_kernel)
+    n = 32
+    kw = dict(on_rack=True, auto_reset=True, settle_steps=300, env_randomizer_mode="GROUND_RANDOMIZER")
+    a = vec_env(n, reset_lookahead=0, **kw)
+    b = vec_env(n, reset_lookahead=2, **kw)
+    a.reset_tensor(); b.reset_tensor()
+    same(a.get_state(), b.get_state(), "state after the reset")
+    t = torch_cuda
+    rng = np.random.default_rng(4)
+    ended = 0
+    for k in range(160):
+        if k % 8 == 3:
+            idx = rng.choice(n, 6, replace=False).tolist()
+            for v in (a, b):
+                v.set_rack(False, indices=idx)
+                s = v.get_state().clone()
+                s[idx, 2] = 0.05                 # below the fallen height: the task ends these episodes in this step
+                v.set_state(s)
+        act = t.from_numpy(rng.uniform(-1, 1, (n, a.action_dim)).astype(np.float32)).to(a.device)
+        ra = [x.clone() for x in a.step_tensor(act)]
+        rb = [x.clone() for x in b.step_tensor(act)]
+        for name, x, y in zip(("obs", "reward", "done", "truncated"), ra, rb):
+            same(x, y, f"{name}, step {k}")
+        same(a.get_state(), b.get_state(), f"state, step {k}")
+        same(a.get_info("rack"), b.get_info("rack"), f"rack info, step {k}")
+        ended += int(ra[2].sum().item())
+    assert ended >= 60, ended
+    served, settled = b.counter("lookahead_served"), b.counter("lookahead_settled")
+    assert settled > 0 and served > n, (served, settled)        # the settle lanes delivered, resets took their states
+    assert b.counter("reset_stalls") > 0                          # ... and some resets settled in place next to them
+    assert (b.get_info("rack").cpu().numpy()[:, 0] >= 0.0).all()
+
+
+def test_auto_reset_hangs_the_robot_again(torch_cuda):
+    n = 16
+    v = vec_env(n, on_rack=True, auto_reset=True, reset_lookahead=0)
+    v.reset_tensor()
+    v.set_rack(False, indices=[2, 5])
+    s = v.get_state().clone()
+    s[2, 2] = 0.05                      # below the fallen height: the task ends the episode in the next step
+    v.set_state(s)
+    t = torch_cuda
+    _, _, done, _ = v.step_tensor(t.zeros((n, v.action_dim), device=v.device))
+    assert bool(done[2]) and not bool(done[5])
+    info = v.get_info("rack").cpu().numpy()
+    assert info[2, 0] == 1.0 and info[5, 0] == 0.0
+    assert abs(v.get_state()[2, 2].item() - 1.0) < 2e-3
+
+
+def test_seed_keeps_the_rack(torch_cuda):
+    v = vec_env(16, on_rack=True, reset_lookahead=0)
+    v.seed(5)
+    v.reset_tensor()
+    info = v.get_info("rack").cpu().numpy()
+    assert (info[:, 0] == 1.0).all() and (info[:, 7] < 2e-3).all()
+    assert np.allclose(info[:, 3], info[0, 3], rtol=1e-2) and info[0, 3] > 100.0
+
+
+def test_refusals(torch_cuda):
+    v = vec_env(16)
+    with pytest.raises(RuntimeError, match="on_rack"):
+        v.set_rack(False)
+    with pytest.raises(RuntimeError, match="rack"):
+        v.get_info("rack")
+    with pytest.raises(NotImplementedError, match="payload"):
+        vec_env(16, on_rack=True, payload="soft")
+
+
+def test_gym_env_on_rack(torch_cuda):
+    """QuadrupedGymEnv(on_rack=True): reset, 100 steps of zero action on the rack, render() and the sub-step callback; released, the robot
+    falls and lands like any other"""
+    from qs_amd.env.quadruped_gym_env import QuadrupedGymEnv
+    env = QuadrupedGymEnv(on_rack=True, task_env="NO_TASK", noise=False)
+    assert env.get_quadruped_config()["on_rack"] is True
+    assert env.robot._GetDefaultInitPosition() == [0, 0, 1]
+    env.reset()
+    z = np.zeros(env.action_space.shape, np.float32)
+    for _ in range(100):
+        env.step(z)
+    pos = np.array(env.robot.GetBasePosition())
+    assert np.linalg.norm(pos - [0.0, 0.0, 1.0]) < 2e-3, pos
+    info = env._vec.get_info("rack")[0].cpu().numpy()
+    assert info[0] == 1.0 and abs(info[3] - 12.0 * 9.8) < 0.05 * 12.0 * 9.8, info
+    img = env.render()
+    assert img.ndim == 3 and img.shape[2] == 3
+    calls = []
+    env.set_sub_step_callback(lambda: calls.append(env.robot.GetBasePosition()[2]))
+    env.step(z)
+    assert len(calls) == env._vec.cfg.action_repeat
+    env.set_sub_step_callback(None)
+    env.set_rack(False)
+    for _ in range(150):
+        env.step(z)
+    assert env.robot.GetBasePosition()[2] < 0.45
+    assert env.robot.GetContactInfo()[0] >= 2         # down on the floor
+
+
+def test_set_rack_never_waits_for_the_device(torch_cuda):
+    t = torch_cuda
+    n = 64
+    v = vec_env(n, on_rack=True, reset_lookahead=0)
+    v.reset_tensor()
+    act = t.zeros((n, v.action_dim), device=v.device)
+    t.cuda.synchronize()
+    t.cuda.set_sync_debug_mode("error")
+    try:
+        for k in range(4):
+            v.set_rack(False, indices=[1, 5, 9])
+            v.step_tensor(act)
+            v.set_rack(True)
+            v.step_tensor(act)
+    finally:
+        t.cuda.set_sync_debug_mode("default")
+    assert (v.get_info("rack").cpu().numpy()[:, 0] == 1.0).all()
