@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """What quadruped_spring/load_model.py:109-137 does with one PyBullet environment, on 8192 environments at once.
 
-    python examples/rollout.py [--envs 8192] [--steps 1000] [--wrapper LANDING]
+    python examples/rollout.py [--envs 8192] [--steps 1000] [--wrapper LANDING] [--device-policy [--model PATH]]
 
-`policy` stands in for `model.predict`: any callable from an observation batch to an action batch.  With --device-policy the
-loop never leaves the GPU (step_tensor); without it the SB3 numpy convention is used (VecEnv.step, infos with
-"terminal_observation" / "TimeLimit.truncated")."""
+With --device-policy the loop never leaves the GPU: `model.predict` is a DevicePolicy (one HIP launch; an SB3 PPO model .zip given with
+--model, random 64-64 tanh weights otherwise) and the step is step_tensor.  Without it `policy` stands in for `model.predict` and the SB3
+numpy convention is used (VecEnv.step, infos with "terminal_observation" / "TimeLimit.truncated")."""
 import argparse
 import os
 import sys
@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(REPO, "quadruped-springs_amd"))
 import numpy as np
 import torch
 
-from qs_amd import DeviceVecNormalize, QuadrupedVecEnv
+from qs_amd import DevicePolicy, DeviceVecNormalize, QuadrupedVecEnv
 
 
 def main():
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--wrapper", default=None, help="LANDING | LANDING2 | LANDING_BACKFLIP | LANDING_CONTINUOUS | GO_TO_REST")
     ap.add_argument("--device-policy", action="store_true")
+    ap.add_argument("--model", default=None, help="an SB3 PPO model .zip for --device-policy (default: random 64-64 tanh weights)")
     args = ap.parse_args()
     env_kwargs = dict(task_env="JUMPING_IN_PLACE", observation_space_mode="PPO_BASIC", action_space_mode="SYMMETRIC", motor_control_mode="PD",
                       enable_springs=True, enable_action_filter=True, env_randomizer_mode="GROUND_RANDOMIZER")   # an args.yml of the reference
@@ -34,7 +35,13 @@ def main():
     rng = np.random.default_rng(0)
     returns, lengths, ep_ret, ep_len = [], [], np.zeros(args.envs), np.zeros(args.envs, int)
     if args.device_policy:
-        policy = lambda obs: torch.tanh(obs[:, :6] * 3.0)       # stand-in for a network living on the GPU
+        if args.model:
+            model = DevicePolicy.load(args.model, num_envs=args.envs)
+        else:
+            torch.manual_seed(0)
+            model = DevicePolicy(env.obs_dim, env.action_dim, net_arch=(64, 64), activation="tanh", num_envs=args.envs)
+            model.set_params(torch.randn(model.n_params, device="cuda") * 0.1)
+        policy = model.act                                      # model.predict(obs, deterministic=True) without the host trip
         obs = env.reset_tensor()
         torch.cuda.synchronize()
         t0 = time.perf_counter()

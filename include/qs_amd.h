@@ -18,6 +18,7 @@
  *   qs_set_params  set_spring_stiffness/damping, changeDynamics(lateralFriction), kp/kd swaps of the landing wrappers
  *                                                                 env/quadruped.py:732-742, env/wrappers/landing_wrapper.py:22-30
  *   qs_render      QuadrupedGymEnv.render(mode="rgb_array")      env/quadruped_gym_env.py:334-335, utils/camera.py:35-59
+ *   qs_policy_act  model.predict(obs, deterministic=...)          load_model.py:132 (SB3 BasePolicy.predict; sb3_contrib ARS.evaluate_candidates)
  *
  * Conventions
  *   - plain pointers and sizes only; all array arguments are DEVICE pointers (HIP) owned by the caller, row-major,
@@ -382,12 +383,48 @@ int qs_render(qs_handle* h, const int32_t* env_ids, int m, const qs_camera* cam,
 int qs_render_states(const float* states, const float* params, int m, const qs_camera* cam, int width, int height,
                      uint32_t* rgba, float* depth, int32_t* seg, void* stream);
 
+/* ---- Policy inference (load_model.py:132 `action, _ = model.predict(obs, deterministic=True)`: SB3 BasePolicy.predict on a PPO MlpPolicy
+ * -- two tanh layers of 64 -- or an sb3_contrib ARS policy -- linear without bias, or a small MLP; and sb3_contrib ARS.evaluate_candidates,
+ * which runs one perturbed parameter vector per episode).  One launch computes for every environment i, with policy p = i / (n_envs / n_policies):
+ *     h = obs[i];  h <- act(W_l[p] h + b_l[p]) for each hidden layer;  mean = W_out[p] h + b_out[p]  (tanh of it under squash_output)
+ *     a = mean + exp(log_std) * eps[i]                          if eps != NULL (DiagGaussianDistribution.sample with the caller's noise)
+ *     log_prob[i] = sum_j (-eps_ij^2 / 2 - log_std_j - log(2 pi) / 2)      if asked for (Normal(mean, std).log_prob(a).sum(-1), before clipping)
+ *     actions[i] = clamp(a, clip_lo, clip_hi)                   BasePolicy.predict clips to the action Box;  mean_out[i] = mean (not clipped)
+ * in float32, every pre-activation one fmaf chain in ascending k that starts from the bias (csrc/qs_policy.h), so an environment's result does
+ * not depend on the other environments of the batch.  Parameters: ONE device array [n_policies][qs_policy_param_count()], per policy layer by
+ * layer the weight [out][in] row-major and then the bias [out] (none at all without has_bias): torch.nn.utils.parameters_to_vector over a
+ * Sequential of Linear layers, the flat theta that ARS perturbs.  Limits: obs_dim <= 64, at most QS_POLICY_MAX_HIDDEN hidden layers, every
+ * width and action_dim <= 256, n_policies divides n_envs; a descriptor outside them fails with text in qs_last_error().
+ * Policy handles are independent of simulation handles. */
+#define QS_POLICY_MAX_HIDDEN 4
+enum { QS_POLICY_ACT_NONE = 0, QS_POLICY_ACT_TANH = 1, QS_POLICY_ACT_RELU = 2 };
+typedef struct qs_policy qs_policy;
+typedef struct qs_policy_desc {
+    int32_t n_envs, n_policies, obs_dim, action_dim, n_hidden, hidden[QS_POLICY_MAX_HIDDEN];
+    int32_t activation;      /* QS_POLICY_ACT_*: of the hidden layers */
+    int32_t squash_output;   /* tanh on the last layer's output (SB3 squash_output) */
+    int32_t has_bias;        /* 0: no layer has a bias (sb3_contrib's linear ARS policy) */
+    float clip_lo, clip_hi;  /* the action Box; -3e38 / 3e38 for none (finite: the kernels are built with -ffinite-math-only) */
+} qs_policy_desc;
+int qs_policy_create(const qs_policy_desc* d, int device, qs_policy** out);
+void qs_policy_destroy(qs_policy* p);
+int qs_policy_set_stream(qs_policy* p, void* hip_stream);
+/* parameters of ONE policy (a negative code for a null handle) */
+int qs_policy_param_count(const qs_policy* p);
+/* dev_params [n_policies][param_count] in device memory.  The handle KEEPS THE POINTER and copies nothing: every later qs_policy_act reads
+ * the array as it is then (an ARS population rewritten in place needs no second call); the caller keeps it alive until the handle is
+ * destroyed or given another array. */
+int qs_policy_set_params(qs_policy* p, const float* dev_params);
+/* obs [N, obs_dim], eps [N, action_dim] or NULL (deterministic), log_std [action_dim] (required with eps), actions [N, action_dim],
+ * mean_out [N, action_dim] or NULL, log_prob [N] or NULL (needs eps).  Stream-ordered, no host synchronisation, no allocation. */
+int qs_policy_act(qs_policy* p, const float* obs, const float* eps, const float* log_std, float* actions, float* mean_out, float* log_prob);
+
 const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 8
 int qs_abi_version(void);
 

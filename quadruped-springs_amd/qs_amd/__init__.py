@@ -14,6 +14,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch / a GP
     if name == "DeviceVecNormalize":
         from .vec_normalize import DeviceVecNormalize
         return DeviceVecNormalize
+    if name == "DevicePolicy":
+        from .policy import DevicePolicy
+        return DevicePolicy
     if name == "ShardedVecEnv":
         from .sharded import ShardedVecEnv
         return ShardedVecEnv

@@ -17,6 +17,7 @@ EXPORTS = (
     "qs_settle_lanes", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_create_ex", "qs_set_rack", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
     "qs_norm_create", "qs_norm_destroy", "qs_norm_dims", "qs_norm_set_stream", "qs_norm_set_stats", "qs_norm_get_stats", "qs_norm_reset", "qs_norm_step",
     "qs_norm_step_io", "qs_host_set_norm",
+    "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
 )
 
 
@@ -39,6 +40,13 @@ class QsCamera(C.Structure):
     """qs_camera (include/qs_amd.h): a camera of qs_render / qs_render_states."""
     _fields_ = [("target", C.c_float * 3), ("distance", C.c_float), ("yaw_deg", C.c_float), ("pitch_deg", C.c_float), ("fov_deg", C.c_float),
                 ("near_clip", C.c_float), ("far_clip", C.c_float), ("follow_base", C.c_int32), ("draw_payload", C.c_int32)]
+
+
+class QsPolicyDesc(C.Structure):
+    """qs_policy_desc (include/qs_amd.h): the network of qs_policy_create."""
+    _fields_ = [("n_envs", C.c_int32), ("n_policies", C.c_int32), ("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32 * 4), ("activation", C.c_int32), ("squash_output", C.c_int32), ("has_bias", C.c_int32),
+                ("clip_lo", C.c_float), ("clip_hi", C.c_float)]
 
 
 class QsRack(C.Structure):
@@ -108,6 +116,14 @@ def load():
     lib.qs_norm_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.qs_norm_step_io.argtypes = [vp, C.POINTER(NormIO), i32, i32, i32]
     lib.qs_host_set_norm.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    if hasattr(lib, "qs_policy_create"):   # (added under ABI 8; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
+        lib.qs_policy_create.argtypes = [C.POINTER(QsPolicyDesc), i32, C.POINTER(vp)]
+        lib.qs_policy_destroy.argtypes = [vp]
+        lib.qs_policy_destroy.restype = None
+        lib.qs_policy_set_stream.argtypes = [vp, vp]
+        lib.qs_policy_param_count.argtypes = [vp]
+        lib.qs_policy_set_params.argtypes = [vp, vp]
+        lib.qs_policy_act.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)
