@@ -1,6 +1,7 @@
 // qs_env.h -- one QuadrupedGymEnv.step() / reset() per environment record, on top of Sim<T>::substep.
 // Reference lines are relative to quadruped_spring/ ; the same restatement in float64 lives in oracle/qso_env.c.
 #pragma once
+#include <type_traits>
 #include "qs_core.h"
 
 namespace qs {
@@ -969,5 +970,76 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false, bool 
         write_obs(cfg, obs, s, o, t, env_id, (uint32_t)total);
     }
 };
+
+// ---- which builds of Env a handle runs.  THE statement of the rule: the launches of qs_hip.hip and the host emulation (tests/emu) both
+// select through Build::of and with_build, and run the env step through step_hand_over.
+//   full build     Env<T, cone, false, false, rack>: resets, in-step settle, look-ahead fill, the rest of a handed-over step
+//   common path    Env<T, cone, true, soft, rack>, where `soft` says that it holds six fixed-constraint rows on the trunk -- the payload
+//                  block's (cfg.payload_soft) or the rack's -- which only the implicit cone's common-path solve has room for.  Under the
+//                  friction pyramid such a handle runs the <false, false> build, whose first substep hands over.
+//   block          the records' block slots (R_BLOCK: the payload block's state, or the rack's RK_*) are live and travel with the tile
+struct Build {
+    bool cone, soft, rack, block;
+    static QS_FN Build of(const qs_config& cfg, bool rack_on) {
+        Build b;
+        b.cone = cfg.friction_cone != 0; b.rack = rack_on;
+        b.block = rack_on || cfg.payload_soft;
+        b.soft = b.cone && b.block;
+        return b;
+    }
+    QS_FN int rec_stride() const { return block ? (int)QS_REC_END : (int)QS_INFO_END; }   // floats between two records of a step kernel's tile in LDS
+    QS_FN size_t step_lds_bytes() const { return (size_t)QS_ENVS_PER_WAVE * (rec_stride() + QS_MAX_OBS + 12) * sizeof(float); }   // + observation and action rows
+};
+// f(cone, soft, rack) with the handle's flags as std::integral_constant<bool, ...>: the five builds that exist
+template <class F> inline void with_build(const Build& b, F&& f) {
+    using Y = std::true_type; using N = std::false_type;
+    if (b.rack) { if (b.cone) f(Y(), Y(), Y()); else f(N(), N(), Y()); }
+    else if (b.soft) f(Y(), Y(), N());
+    else if (b.cone) f(Y(), N(), N());
+    else f(N(), N(), N());
+}
+
+// One env step as the step kernels run it: the common-path build, and from the substep where that gave up (resume >= 0) the full build.
+// Takes Env::step's arguments; returns the step's results with the common-path build's `resume` (-1: not handed over).
+// (step_body, qs_hip.hip, has these lines in place: called through this function its kernels come out with another register allocation)
+template <class T, bool CONE, bool SOFT, bool RACK, bool LEAN>
+QS_FN typename Env<T, CONE, false, false, RACK>::StepOut step_hand_over(const qs_config& cfg, float* rec, const float* act_row, float* obs, uint32_t env_id, int settle_n = 0,
+                                                                        float* trace = nullptr, bool any_trace = false, const float* demo_rows = nullptr, int demo_len = 0,
+                                                                        const float* push = nullptr) {
+    using EF = Env<T, CONE, false, false, RACK>;
+    using EH = Env<T, CONE, true, SOFT, RACK>;
+    typename EF::StepOut r;
+    {
+        const typename EH::StepOut rh = EH::template step<false, LEAN>(cfg, rec, act_row, obs, env_id, settle_n, trace, any_trace, demo_rows, demo_len, 0, push);
+        r.reward = rh.reward; r.done = rh.done; r.trunc = rh.trunc; r.resume = rh.resume;
+    }
+    if (__builtin_expect(r.resume >= 0, 0)) {
+        const int at = r.resume;
+        r = EF::template step<true>(cfg, rec, act_row, obs, env_id, settle_n, trace, any_trace, demo_rows, demo_len, at, push);
+        r.resume = at;
+    }
+    return r;
+}
+
+// ---- plain rows of a record that a kernel (one thread per record) and the host emulation both write
+// a fresh record behind its zero fill (k_init): no episode yet, the robot standing at the spawn pose
+QS_FN void init_record_row(float* r) {
+    r[R_EPISODE] = i2f(-1);
+    r[R_QUAT + 3] = 1.0f; r[R_POS + 2] = 0.32f; r[R_TASK + T_FIRST_JUMP] = 1.0f;
+    for (int L = 0; L < 4; L++) { r[R_Q + 3 * L + 1] = 0.78539816339f; r[R_Q + 3 * L + 2] = -1.57079632679f; }
+}
+// qs_set_rack: hang or release; the rack's impulses start from zero either way
+QS_FN void set_rack_row(float* rec, int hung) {
+    float* b = rec + R_BLOCK;
+    b[RK_HUNG] = hung ? 1.0f : 0.0f;
+    for (int k = 0; k < 6; k++) b[RK_LAM + k] = 0.0f;
+}
+// QS_INFO_RACK: hung, force 3, torque 3 (the six impulses / dt), |base origin - anchor|
+QS_FN void rack_info_row(const float* r, float inv_dt, float ax, float ay, float az, float* o) {
+    o[0] = r[R_BLOCK + RK_HUNG];
+    for (int k = 0; k < 6; k++) o[1 + k] = r[R_BLOCK + RK_LAM + k] * inv_dt;
+    const float dx = r[R_POS] - ax, dy = r[R_POS + 1] - ay, dz = r[R_POS + 2] - az;
+    o[7] = sqrtf(dx * dx + dy * dy + dz * dz);
+}
 
 }  // namespace qs

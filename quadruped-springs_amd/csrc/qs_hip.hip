@@ -248,11 +248,7 @@ __global__ __launch_bounds__(QS_WAVE, 1) void k_init(const qs_config* __restrict
     float* r = recs + (size_t)env * QS_REC;
     for (int i = threadIdx.x & 3; i < QS_REC_END; i += 4) r[i] = 0.0f;
     LaneDev::sync();
-    if ((threadIdx.x & 3) == 0) {
-        r[R_EPISODE] = qs::i2f(-1);
-        r[R_QUAT + 3] = 1.0f; r[R_POS + 2] = 0.32f; r[R_TASK + T_FIRST_JUMP] = 1.0f;
-        for (int L = 0; L < 4; L++) { r[R_Q + 3 * L + 1] = 0.78539816339f; r[R_Q + 3 * L + 2] = -1.57079632679f; }
-    }
+    if ((threadIdx.x & 3) == 0) qs::init_record_row(r);
     E::randomize(cfg, r, (uint32_t)(env + cfg.env_id_offset), -1, true);
 }
 
@@ -277,7 +273,7 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     // LDS (sized at launch, step_lds_bytes): the 16 records at stride `ls`, the observation rows, the action rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     const qs_config& cfg = *cfgp;
-    const int ls = (RACK || cfg.payload_soft) ? (int)QS_REC_END : (int)QS_INFO_END;
+    const int ls = (RACK || cfg.payload_soft) ? (int)QS_REC_END : (int)QS_INFO_END;   // = qs::Build::rec_stride (spelled out: see below)
     float* const s_rec = s_dyn;
     float* const s_obs = s_dyn + QS_ENVS_PER_WAVE * ls;
     float* const s_act = s_obs + QS_ENVS_PER_WAVE * QS_MAX_OBS;
@@ -345,6 +341,8 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     // The env step starts in the common-path build; a wave in which some environment needs a rare path goes on in the full build from the
     // substep where that shows (Env::step: the state of that moment is in the LDS record, the prologue's results in the observation row).
     // A payload_soft handle under the friction pyramid has its block's rows in no common-path build: its first substep already hands over.
+    // These lines ARE qs::step_hand_over (qs_env.h), which the host emulation runs, and `ls` above is qs::Build::rec_stride: going through
+    // either function, however it is inlined, changes the register allocation of all ten step kernels.  Change them together.
     typename E::StepOut r;
     {
         const typename EH::StepOut rh = EH::template step<false, QS_LEAN_WAVES(WAVES)>(cfg, rec, s_act + slot * 12, ob, gid, settle_n, trow, any_trace, demo.rows, demo.length, 0, prow);
@@ -659,21 +657,13 @@ __global__ void k_task_info(const float* __restrict__ recs, int n, float* __rest
 __global__ void k_set_rack(float* __restrict__ recs, int n, const uint8_t* __restrict__ mask, int hung) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n || (mask && !mask[e])) return;
-    float* b = recs + (size_t)e * QS_REC + R_BLOCK;
-    b[RK_HUNG] = hung ? 1.0f : 0.0f;
-    for (int k = 0; k < 6; k++) b[RK_LAM + k] = 0.0f;
+    qs::set_rack_row(recs + (size_t)e * QS_REC, hung);
 }
 
-// QS_INFO_RACK: hung, force 3, torque 3 (the six impulses / dt), |base origin - anchor|
 __global__ void k_rack_info(const float* __restrict__ recs, int n, float inv_dt, float ax, float ay, float az, float* __restrict__ out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    const float* r = recs + (size_t)e * QS_REC;
-    float* o = out + (size_t)e * 8;
-    o[0] = r[R_BLOCK + RK_HUNG];
-    for (int k = 0; k < 6; k++) o[1 + k] = r[R_BLOCK + RK_LAM + k] * inv_dt;
-    const float dx = r[R_POS] - ax, dy = r[R_POS + 1] - ay, dz = r[R_POS + 2] - az;
-    o[7] = sqrtf(dx * dx + dy * dy + dz * dz);
+    qs::rack_info_row(recs + (size_t)e * QS_REC, inv_dt, ax, ay, az, out + (size_t)e * 8);
 }
 
 #ifdef QS_ISA_ONLY
@@ -730,6 +720,7 @@ static int sensor_dim(int s) {
     }
 }
 static int n_waves(int n) { return (n + QS_ENVS_PER_WAVE - 1) / QS_ENVS_PER_WAVE; }
+static qs::Build handle_build(const qs_handle* h) { return qs::Build::of(h->cfg, h->rack.on != 0); }   // which kernels the handle launches (qs_env.h)
 
 #define QS_STR2(x) #x
 #define QS_STR(x) QS_STR2(x)
@@ -862,10 +853,10 @@ static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs
         QS_HIP(hipMemsetAsync(h->d_stage_jobs, 0, (size_t)QS_COHORTS * h->slice * sizeof(int2), h->stream));
 
         const unsigned fill_grid = (unsigned)((n * K + QS_ENVS_PER_WAVE - 1) / QS_ENVS_PER_WAVE);
-        if (h->rack.on && cfg->friction_cone) hipLaunchKernelGGL((k_lookahead_fill_rack<true>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
-        else if (h->rack.on) hipLaunchKernelGGL((k_lookahead_fill_rack<false>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
-        else if (cfg->friction_cone) hipLaunchKernelGGL((k_lookahead_fill<true>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
-        else hipLaunchKernelGGL((k_lookahead_fill<false>), dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(fill_grid), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->la); };
+        qs::with_build(handle_build(h), [&](auto cone, auto, auto rack) {
+            if constexpr (rack()) launch(k_lookahead_fill_rack<cone()>); else launch(k_lookahead_fill<cone()>);
+        });
         QS_HIP(hipGetLastError());
         h->lanes_on = 1;
     }
@@ -915,13 +906,12 @@ int qs_enable_timing(qs_handle* h, int on) {
 }
 
 static void launch_reset(qs_handle* h, const uint8_t* mask, const float* states) {
-#define QS_LAUNCH_RESET(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, \
-                                                   h->d_stats, states, h->la, h->d_push)
-    if (h->rack.on && h->cfg.friction_cone) QS_LAUNCH_RESET(k_reset_rack<true>);
-    else if (h->rack.on) QS_LAUNCH_RESET(k_reset_rack<false>);
-    else if (h->cfg.friction_cone) QS_LAUNCH_RESET(k_reset<true>);
-    else QS_LAUNCH_RESET(k_reset<false>);
-#undef QS_LAUNCH_RESET
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(n_waves(h->cfg.n_envs)), dim3(QS_WAVE), 0, h->stream, h->d_cfg, h->d_rec, mask, h->d_obs, h->d_stats, states, h->la, h->d_push);
+    };
+    qs::with_build(handle_build(h), [&](auto cone, auto, auto rack) {
+        if constexpr (rack()) launch(k_reset_rack<cone()>); else launch(k_reset<cone()>);
+    });
 }
 
 int qs_reset(qs_handle* h, const uint8_t* mask) {
@@ -1024,19 +1014,15 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     // more waves than SIMDs: the two-waves-per-SIMD build of the same body (see k_step_dense) instead of a second round of one-wave-per-
     // SIMD workgroups (N = 12288 with its settle lanes: 0.109 ms in two rounds)
     const bool dense = h->step_variant == 2 || (h->step_variant == 0 && (lanes.n_env_waves > h->n_simd || !lanes_fit));
-    const size_t lds = (size_t)QS_ENVS_PER_WAVE * (((h->cfg.payload_soft || h->rack.on) ? QS_REC_END : QS_INFO_END) + QS_MAX_OBS + 12) * sizeof(float);
-#define QS_LAUNCH_STEP(KERNEL) hipLaunchKernelGGL((KERNEL), dim3(grid), dim3(QS_WAVE), lds, h->stream, h->d_cfg, h->d_rec, actions, obs, rew, done, trunc, \
-                                                 h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push)
-#define QS_PICK(C, S) { if (dense) QS_LAUNCH_STEP((k_step_dense<C, S>)); else QS_LAUNCH_STEP((k_step<C, S>)); }
-#define QS_PICK_RACK(C) { if (dense) QS_LAUNCH_STEP((k_step_dense_rack<C>)); else QS_LAUNCH_STEP((k_step_rack<C>)); }
-    if (h->rack.on && h->cfg.friction_cone) QS_PICK_RACK(true)
-    else if (h->rack.on) QS_PICK_RACK(false)
-    else if (h->cfg.friction_cone && h->cfg.payload_soft) QS_PICK(true, true)
-    else if (h->cfg.friction_cone) QS_PICK(true, false)
-    else QS_PICK(false, false)
-#undef QS_PICK_RACK
-#undef QS_PICK
-#undef QS_LAUNCH_STEP
+    const qs::Build build = handle_build(h);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(QS_WAVE), build.step_lds_bytes(), h->stream, h->d_cfg, h->d_rec, actions, obs, rew, done, trunc,
+                           h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push);
+    };
+    qs::with_build(build, [&](auto cone, auto soft, auto rack) {
+        if constexpr (rack()) launch(dense ? k_step_dense_rack<cone()> : k_step_rack<cone()>);
+        else launch(dense ? k_step_dense<cone(), soft()> : k_step<cone(), soft()>);
+    });
     QS_HIP(hipGetLastError());
     return 0;
 }

@@ -1,45 +1,7 @@
 // qs_emu.cpp -- TEST-ONLY host emulation of the quad-per-environment kernels.
 // Instantiates the kernel arithmetic of quadruped-springs_amd/csrc/qs_env.h with the 4-wide LaneEmu type so that the
 // CPU test-suite (no GPU in the build container) can compare it with the oracle.  Never linked into the product.
-#include <mutex>
-// the many-rows solve's inputs, captured while steps run (qse_rare_capture; tests/test_rare_solver.py): qs_rare.h's emulation twin calls
-// QS_RARE_CAPTURE with them, a no-op unless defined before the kernel headers
-template <class V, class R, class P> static void rare_capture(const V& mu, const R* xr, const P* pay, const V& warm);
-#define QS_RARE_CAPTURE(cfg, mu, xr, pay, mine, warm) rare_capture(mu, xr, pay, warm)
 #include "qs_emu.h"
-
-// One environment's row set, laid out as tests/hip/rare_probe.hip takes it: rows [4 legs][12][16] (a Row's fields in struct order), mu,
-// mine, warm [4], the payload rows [59] (w 36, rhs 6, dinv 6, diag 6, rB 3, mI, act), then 1 if the solve had payload rows at all.
-enum { RARE_ROW_F = 16, RARE_ROWS = 4 * 12 * RARE_ROW_F, RARE_ENV = RARE_ROWS, RARE_WARM = RARE_ENV + 2, RARE_PAY = RARE_WARM + 4, RARE_PAY_F = 59,
-       RARE_HAS_PAY = RARE_PAY + RARE_PAY_F, RARE_REC = RARE_HAS_PAY + 1 };
-static std::mutex g_cap_mu;
-static std::vector<float> g_cap;
-static size_t g_cap_max = 0;
-
-template <class V, class R, class P> static void rare_capture(const V& mu, const R* xr, const P* pay, const V& warm) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    if (g_cap.size() >= g_cap_max * RARE_REC) return;
-    float r[RARE_REC] = {};
-    for (int L = 0; L < 4; L++)
-        for (int k = 0; k < 12; k++) {
-            float* q = r + (12 * L + k) * RARE_ROW_F;
-            for (int i = 0; i < 3; i++) { q[i] = xr[k].jq[i].v[L]; q[3 + i] = xr[k].u[i].v[L]; }
-            for (int i = 0; i < 6; i++) q[6 + i] = xr[k].w[i].v[L];
-            q[12] = xr[k].rhs.v[L]; q[13] = xr[k].dinv.v[L]; q[14] = xr[k].act.v[L]; q[15] = xr[k].diag.v[L];
-        }
-    r[RARE_ENV] = mu.v[0]; r[RARE_ENV + 1] = 1.0f;
-    for (int L = 0; L < 4; L++) r[RARE_WARM + L] = warm.v[L];
-    if (pay) {
-        float* q = r + RARE_PAY;
-        for (int k = 0; k < 6; k++) {
-            for (int i = 0; i < 6; i++) q[6 * k + i] = pay->w[k][i].v[0];
-            q[36 + k] = pay->rhs[k].v[0]; q[42 + k] = pay->dinv[k].v[0]; q[48 + k] = pay->diag[k].v[0];
-        }
-        q[54] = pay->rB.x.v[0]; q[55] = pay->rB.y.v[0]; q[56] = pay->rB.z.v[0]; q[57] = pay->mI.v[0]; q[58] = pay->act.v[0];
-        r[RARE_HAS_PAY] = 1.0f;
-    }
-    g_cap.insert(g_cap.end(), r, r + RARE_REC);
-}
 
 template <bool CONE> static void rare_solve_impl(const qs_config& cfg, int n_envs, const float* rows, const float* env, const float* warm, const float* pay,
                                                  float* lam12, float* plam) {
@@ -75,117 +37,131 @@ template <bool CONE> static void rare_solve_impl(const qs_config& cfg, int n_env
 
 static void init_record(const qs_config& cfg, float* r, int env) {
     memset(r, 0, QS_REC * sizeof(float));
-    r[R_EPISODE] = qs::i2f(-1);
-    r[R_QUAT + 3] = 1.0f; r[R_POS + 2] = 0.32f; r[R_TASK + T_FIRST_JUMP] = 1.0f;
-    for (int L = 0; L < 4; L++) { r[R_Q + 3 * L + 1] = 0.78539816339f; r[R_Q + 3 * L + 2] = -1.57079632679f; }
+    qs::init_record_row(r);
     E::randomize(cfg, r, (uint32_t)(env + cfg.env_id_offset), -1, true);
 }
 
 template <class EV> static void phys_step_impl(Emu* e, int i, const float* tau12) {
-    float* rec = &e->rec[(size_t)i * QS_REC];
+    const qs_config& cfg = e->dc.cfg;
+    float* rec = e->record(i);
     typename EV::S::State s; typename EV::S::Par P; typename EV::S::Out o;
-    EV::load_state(rec, s); EV::load_par(e->cfg, rec, P);
+    EV::load_state(rec, s); EV::load_par(cfg, rec, P);
     V4 tau[3];
     for (int j = 0; j < 3; j++) { tau[j] = LaneEmu::ld_leg(tau12, j, 3); o.tau_pd[j] = V4(0.0f); o.tau_spring[j] = V4(0.0f); }
-    EV::S::substep(e->cfg, P, s, tau, o, true, e->cfg.payload_soft ? rec + R_BLOCK : nullptr);
+    EV::S::substep(cfg, P, s, tau, o, true, cfg.payload_soft ? rec + R_BLOCK : nullptr);
     EV::store_state(rec, s, o);
+}
+
+template <class EV> static void step_impl(Emu* e, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
+    const qs_config& cfg = e->dc.cfg;
+    for (int i = 0; i < cfg.n_envs; i++) {
+        float* tr = (e->trace && i == e->trace_env) ? e->trace : nullptr;
+        const typename EV::StepOut r = EV::step(cfg, e->record(i), actions + (size_t)i * cfg.action_dim, e->obs_row(i), e->gid(i), 0, tr, tr != nullptr, e->demo.data(), e->demo_len);
+        finish_env_step<EV>(e, i, r, obs, rew, done, trunc);
+    }
 }
 
 extern "C" {
 void* qse_create(const qs_config* cfg) {
     Emu* e = new Emu();
-    e->cfg = *cfg;
+    memset(&e->dc, 0, sizeof(e->dc));
+    e->dc.cfg = *cfg;
+    e->dc.rack_pos[2] = 1.0f; e->dc.rack_quat[3] = 1.0f;   // INIT_RACK_POSITION, INIT_ORIENTATION of the robot config (go1/configs_go1_*.py)
     e->rec.assign((size_t)cfg->n_envs * QS_REC, 0.0f);
     e->obs.assign((size_t)cfg->n_envs * QS_MAX_OBS, 0.0f);
     e->term_obs.assign((size_t)cfg->n_envs * QS_MAX_OBS, 0.0f);
-    for (int i = 0; i < cfg->n_envs; i++) init_record(e->cfg, &e->rec[(size_t)i * QS_REC], i);
+    for (int i = 0; i < cfg->n_envs; i++) init_record(e->dc.cfg, e->record(i), i);
     return e;
 }
 void qse_destroy(void* h) { delete (Emu*)h; }
 int qse_set_trace(void* h, int env, float* rows) { Emu* e = (Emu*)h; e->trace_env = env; e->trace = env >= 0 ? rows : nullptr; return 0; }
-int qse_reset(void* h, const uint8_t* mask) {
+// the handle runs the RACK builds (on = 1) or the plain ones (0; -1: as it is), anchor = position 3, quaternion xyzw 4, or null: keep it --
+// the rack of qs_create_ex.  Returns whether the handle has a rack.
+int qse_rack(void* h, int on, const float* anchor) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++)
-        if (!mask || mask[i]) {
-            if (e->cfg.friction_cone) EC::reset(e->cfg, &e->rec[(size_t)i * QS_REC], &e->obs[(size_t)i * QS_MAX_OBS], (uint32_t)(i + e->cfg.env_id_offset), true);
-            else E::reset(e->cfg, &e->rec[(size_t)i * QS_REC], &e->obs[(size_t)i * QS_MAX_OBS], (uint32_t)(i + e->cfg.env_id_offset), true);
-        }
-    return 0;
+    if (on >= 0) e->rack = on != 0;
+    if (anchor) { memcpy(e->dc.rack_pos, anchor, 3 * sizeof(float)); memcpy(e->dc.rack_quat, anchor + 3, 4 * sizeof(float)); }
+    return e->rack ? 1 : 0;
 }
-// qs_reset_to (k_reset with states): randomizers, the given rigid-body state, task / sensor / filter reset, zero action history
+// qs::Build of a handle (cfg, rack): floats between two records of a step kernel's tile, bytes of its LDS; and the layout's two extents
+int qse_build_stride(const qs_config* cfg, int rack, int* lds_bytes, int* rec_end, int* info_end) {
+    const qs::Build b = qs::Build::of(*cfg, rack != 0);
+    *lds_bytes = (int)b.step_lds_bytes(); *rec_end = QS_REC_END; *info_end = QS_INFO_END;
+    return b.rec_stride();
+}
+// qs_reset_to, or (states null) qs_reset; a handle with a rack: qse_reset_build (qs_emu_step.cpp)
 int qse_reset_to(void* h, const uint8_t* mask, const float* states) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) {
-        if (mask && !mask[i]) continue;
-        float* rec = &e->rec[(size_t)i * QS_REC];
-        const uint32_t gid = (uint32_t)(i + e->cfg.env_id_offset);
-        E::randomize(e->cfg, rec, gid, qs::f2i(rec[R_EPISODE]) + 1, false);
-        memcpy(rec + R_POS, states + (size_t)i * 37, 37 * sizeof(float));
-        for (int k = 0; k < 4; k++) { rec[R_WARM + k] = 0.0f; rec[R_FOOT_FORCE + k] = 0.0f; rec[R_FOOT_CONTACT + k] = 0.0f; }
-        rec[R_N_INVALID] = 0.0f;
-        for (int k = 0; k < 24; k++) rec[R_TAU_PD + k] = 0.0f;
-        if (e->cfg.payload_soft) E::place_block(e->cfg, rec);
-        E::reset(e->cfg, rec, &e->obs[(size_t)i * QS_MAX_OBS], gid, false);
-        for (int k = 0; k < 12 + 24 + 24; k++) rec[R_LAST_ACTION + k] = 0.0f;
-    }
+    if (e->rack) return -1;
+    if (e->dc.cfg.friction_cone) reset_envs<EC>(e, mask, states);
+    else reset_envs<E>(e, mask, states);
     return 0;
 }
+int qse_reset(void* h, const uint8_t* mask) { return qse_reset_to(h, mask, nullptr); }
+// qs_set_rack (k_set_rack)
+int qse_set_rack(void* h, const uint8_t* mask, int hung) {
+    Emu* e = (Emu*)h;
+    for (int i = 0; i < e->dc.cfg.n_envs; i++)
+        if (!mask || mask[i]) qs::set_rack_row(e->record(i), hung);
+    return 0;
+}
+// the QS_INFO_RACK rows [N, 8] (k_rack_info)
+int qse_rack_info(void* h, float* out) {
+    Emu* e = (Emu*)h;
+    for (int i = 0; i < e->dc.cfg.n_envs; i++)
+        qs::rack_info_row(e->record(i), (float)(1.0 / e->dc.cfg.dt), e->dc.rack_pos[0], e->dc.rack_pos[1], e->dc.rack_pos[2], out + (size_t)i * 8);
+    return 0;
+}
+int qse_resume_at_boundary(void) { return (int)E::RESUME_AT_BOUNDARY; }
 int qse_set_demo(void* h, const float* rows, int length) {
     Emu* e = (Emu*)h;
-    e->demo.assign(rows, rows + (size_t)length * (e->cfg.action_dim + 38));
+    e->demo.assign(rows, rows + (size_t)length * (e->dc.cfg.action_dim + 38));
     e->demo_len = length;
     return 0;
 }
 int qse_set_demo_counter(void* h, const uint8_t* mask, const int32_t* values) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++)
+    for (int i = 0; i < e->dc.cfg.n_envs; i++)
         if (!mask || mask[i]) { float* r = &e->rec[(size_t)i * QS_REC + R_DEMO]; r[0] = r[1] = (float)values[i]; }
     return 0;
 }
 int qse_get_obs(void* h, float* obs) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) memcpy(obs + (size_t)i * e->cfg.obs_dim, &e->obs[(size_t)i * QS_MAX_OBS], e->cfg.obs_dim * sizeof(float));
+    for (int i = 0; i < e->dc.cfg.n_envs; i++) memcpy(obs + (size_t)i * e->dc.cfg.obs_dim, &e->obs[(size_t)i * QS_MAX_OBS], e->dc.cfg.obs_dim * sizeof(float));
     return 0;
 }
 // infos[i]["terminal_observation"] of the last episode each environment finished (auto_reset)
 int qse_get_term_obs(void* h, float* obs) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) memcpy(obs + (size_t)i * e->cfg.obs_dim, &e->term_obs[(size_t)i * QS_MAX_OBS], e->cfg.obs_dim * sizeof(float));
+    for (int i = 0; i < e->dc.cfg.n_envs; i++) memcpy(obs + (size_t)i * e->dc.cfg.obs_dim, &e->term_obs[(size_t)i * QS_MAX_OBS], e->dc.cfg.obs_dim * sizeof(float));
     return 0;
 }
 int qse_step(void* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
     Emu* e = (Emu*)h;
-    const int d = e->cfg.action_dim;
-    for (int i = 0; i < e->cfg.n_envs; i++) {
-        float* rec = &e->rec[(size_t)i * QS_REC];
-        float* ob = &e->obs[(size_t)i * QS_MAX_OBS];
-        float* tr = (e->trace && i == e->trace_env) ? e->trace : nullptr;
-        float rw, dn, tc;
-        if (e->cfg.friction_cone) { EC::StepOut r = EC::step(e->cfg, rec, actions + (size_t)i * d, ob, (uint32_t)(i + e->cfg.env_id_offset), 0, tr, tr != nullptr, e->demo.data(), e->demo_len); rw = r.reward.v[0]; dn = r.done.v[0]; tc = r.trunc.v[0]; }
-        else { E::StepOut r = E::step(e->cfg, rec, actions + (size_t)i * d, ob, (uint32_t)(i + e->cfg.env_id_offset), 0, tr, tr != nullptr, e->demo.data(), e->demo_len); rw = r.reward.v[0]; dn = r.done.v[0]; tc = r.trunc.v[0]; }
-        finish_env_step(e, i, rw, dn, tc, obs, rew, done, trunc);
-    }
+    if (e->rack) return -1;
+    if (e->dc.cfg.friction_cone) step_impl<EC>(e, actions, obs, rew, done, trunc);
+    else step_impl<E>(e, actions, obs, rew, done, trunc);
     return 0;
 }
 int qse_get_state(void* h, float* st) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) memcpy(st + (size_t)i * 37, &e->rec[(size_t)i * QS_REC + R_POS], 37 * sizeof(float));
+    for (int i = 0; i < e->dc.cfg.n_envs; i++) memcpy(st + (size_t)i * 37, &e->rec[(size_t)i * QS_REC + R_POS], 37 * sizeof(float));
     return 0;
 }
 int qse_set_state(void* h, const float* st) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) {
+    for (int i = 0; i < e->dc.cfg.n_envs; i++) {
         float* r = &e->rec[(size_t)i * QS_REC];
         memcpy(r + R_POS, st + (size_t)i * 37, 37 * sizeof(float));
         for (int k = 0; k < 4; k++) r[R_WARM + k] = 0.0f;
-        if (e->cfg.payload_soft) E::place_block(e->cfg, r);
+        if (e->dc.cfg.payload_soft) E::place_block(e->dc.cfg, r);
     }
     return 0;
 }
 // the payload block as its own body (cfg.payload_soft): [N, 20], the oracle's qso_get_block row
 int qse_get_block(void* h, float* out) {
     Emu* e = (Emu*)h;
-    for (int i = 0; i < e->cfg.n_envs; i++) memcpy(out + (size_t)i * QS_BLOCK_DIM, &e->rec[(size_t)i * QS_REC + R_BLOCK], QS_BLOCK_DIM * sizeof(float));
+    for (int i = 0; i < e->dc.cfg.n_envs; i++) memcpy(out + (size_t)i * QS_BLOCK_DIM, &e->rec[(size_t)i * QS_REC + R_BLOCK], QS_BLOCK_DIM * sizeof(float));
     return 0;
 }
 float* qse_records(void* h) { return ((Emu*)h)->rec.data(); }
@@ -214,18 +190,10 @@ int qse_rare_solve(const qs_config* cfg, int n_envs, const float* rows, const fl
     else rare_solve_impl<false>(*cfg, n_envs, rows, env, warm, pay, lam12, plam);
     return 0;
 }
-// capture the inputs of the next `max_sets` many-rows solves (0: stop); qse_rare_captured copies them out (RARE_REC floats each) and clears
-int qse_rare_capture(int max_sets) { std::lock_guard<std::mutex> lk(g_cap_mu); g_cap.clear(); g_cap_max = (size_t)(max_sets > 0 ? max_sets : 0); return RARE_REC; }
-int qse_rare_captured(float* out) {
-    std::lock_guard<std::mutex> lk(g_cap_mu);
-    const int n = (int)(g_cap.size() / RARE_REC);
-    if (out) { memcpy(out, g_cap.data(), g_cap.size() * sizeof(float)); g_cap.clear(); g_cap_max = 0; }
-    return n;
-}
 // one physics substep of env `i` under given joint torques (KATs on the kernel arithmetic)
 int qse_phys_step(void* h, int i, const float* tau12) {
     Emu* e = (Emu*)h;
-    if (e->cfg.friction_cone) phys_step_impl<EC>(e, i, tau12);
+    if (e->dc.cfg.friction_cone) phys_step_impl<EC>(e, i, tau12);
     else phys_step_impl<E>(e, i, tau12);
     return 0;
 }

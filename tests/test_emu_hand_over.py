@@ -1,7 +1,7 @@
-"""The step kernels' hand-over on the host (tests/emu/qs_emu_hot.cpp): the common-path build of Env::step that k_step / k_step_dense run
+"""The step kernels' hand-over on the host (tests/emu/qs_emu_step.cpp): the common-path build of Env::step that k_step / k_step_dense run
 first, and the full build's step<true>(..., resume) that goes on from the substep where it gave up, against the full build's step from
 the same records -- bit for bit (qs_env.h, Env::step).  Mid-substep hand-overs (a vote of substep k gave up) and boundary ones (substep
-k - 1 predicted the rare path: RESUME_AT_BOUNDARY), the CONE / SOFT / LEAN builds QS_PICK launches, hand-overs late in a long step, and
+k - 1 predicted the rare path: RESUME_AT_BOUNDARY), the CONE / SOFT / LEAN builds launch_step launches, hand-overs late in a long step, and
 the settle lanes' slices."""
 import numpy as np
 import pytest
@@ -37,7 +37,7 @@ def assert_bitwise(a, b, what):
 
 
 class Pair:
-    """the same configuration twice: `full` steps with the full build (qse_step), `hot` with the step kernel's builds (qse_step_hot)"""
+    """the same configuration twice: `full` steps with the full build (qse_step), `hot` with the step kernel's builds (qse_step_build)"""
 
     def __init__(self, cfg, meta=None, trace_env=None):
         self.cfg = cfg
@@ -237,3 +237,26 @@ def test_settle_slices_hand_over_bit_for_bit(case):
         assert (r == 0).all()
     else:
         assert ((r >= 0) & ((r & p.hot.resume_at_boundary()) == 0)).any()
+
+
+@pytest.mark.parametrize("rack", [False, True])
+@pytest.mark.parametrize("payload", ["weld", "soft"])
+def test_launch_sizes_the_tile_as_the_kernel_strides_it(rack, payload):
+    """step_body spells the record stride of its LDS tile out (going through qs::Build changes the step kernels' register allocation);
+    launch_step sizes the LDS by qs::Build::step_lds_bytes.  The two statements agree for every (rack, payload_soft), and the kernel's
+    line is still the one this test restates."""
+    import os
+    from emu.emu import build_stride
+    if rack and payload == "soft":
+        cfg, _ = build_config(n_envs=16, payload="weld", **RAW)     # (qs_create_ex refuses the pair; the rule is total all the same)
+        cfg.payload_soft = 1
+    else:
+        cfg, _ = build_config(n_envs=16, payload=payload, **RAW)
+    assert bool(cfg.payload_soft) == (payload == "soft")
+    stride, lds_bytes, rec_end, info_end = build_stride(cfg, rack)
+    src = open(os.path.join(os.path.dirname(__file__), "..", "quadruped-springs_amd", "csrc", "qs_hip.hip")).read()
+    assert "const int ls = (RACK || cfg.payload_soft) ? (int)QS_REC_END : (int)QS_INFO_END;" in src
+    assert "s_obs = s_dyn + QS_ENVS_PER_WAVE * ls;" in src and "s_act = s_obs + QS_ENVS_PER_WAVE * QS_MAX_OBS;" in src
+    assert stride == (rec_end if (rack or cfg.payload_soft) else info_end) and info_end < rec_end
+    max_obs = 64    # QS_MAX_OBS (include/qs_amd.h); the action rows: 12 floats
+    assert lds_bytes == 16 * (stride + max_obs + 12) * 4

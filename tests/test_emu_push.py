@@ -1,4 +1,4 @@
-"""External pushes on the trunk (qs_set_external_wrench) in the host emulation (tests/emu/qs_emu_push.cpp): the velocity change of one
+"""External pushes on the trunk (qs_set_external_wrench) in the host emulation (tests/emu/qs_emu_step.cpp): the velocity change of one
 substep against the float64 mass matrix of the oracle, the common-path build's hand-over under a push against the full build bit for bit,
 a zero-duration push against the push-free step, and the bindings' refusals.  No GPU."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The rack (on_rack=True: qs_create_ex with a qs_rack) in the host emulation (tests/emu/qs_emu_rack.cpp): the velocity change of one substep
+"""The rack (on_rack=True: qs_create_ex with a qs_rack) in the host emulation (tests/emu/qs_emu_step.cpp): the velocity change of one substep
 against a float64 PGS of the six rows through the oracle's mass matrix, the reported reaction, the common-path build's hand-over to the full
 build bit for bit with a joint at its stop, the many-rows solve's rack rows against tests/rare_ref.py, a static hang after a reset, a
 release and a re-hang, and the bindings' refusals.  No GPU."""

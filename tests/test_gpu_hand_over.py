@@ -10,7 +10,7 @@ from test_gpu_round2 import fallen_states, vec_env
 pytestmark = pytest.mark.gpu
 
 ON_ITS_SIDE = [0.6631, 0.0, 0.0, 0.7485]   # roll ~1.45 rad
-DROP_Z = 0.52                              # first body contact at substep ~274 of the first step (qse_step_hot: resume)
+DROP_Z = 0.52                              # first body contact at substep ~274 of the first step (qse_step_build: resume)
 
 
 @pytest.fixture(scope="module")
