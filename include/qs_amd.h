@@ -419,13 +419,50 @@ int qs_policy_set_params(qs_policy* p, const float* dev_params);
  * mean_out [N, action_dim] or NULL, log_prob [N] or NULL (needs eps).  Stream-ordered, no host synchronisation, no allocation. */
 int qs_policy_act(qs_policy* p, const float* obs, const float* eps, const float* log_std, float* actions, float* mean_out, float* log_prob);
 
+/* ---- PPO collection on the device (stable_baselines3 1.5 as remembered: OnPolicyAlgorithm.collect_rollouts, ActorCriticPolicy.forward,
+ * RolloutBuffer.add / compute_returns_and_advantage).  Actor and critic are two separate networks (MlpPolicy's default
+ * net_arch = dict(pi=[64, 64], vf=[64, 64])), each described like a qs_policy and computed by the same chain (csrc/qs_policy.h, csrc/qs_ppo.h):
+ * action, value and log-prob of an environment are the bits two qs_policy handles give for the same parameters.  Shared trunks are not
+ * supported.  Handles are independent of simulation handles; every call is stream-ordered, without host synchronisation or allocation. */
+typedef struct qs_ac qs_ac;
+/* ActorCriticPolicy.__init__ for an MlpPolicy with separate trunks.  Refuses, with text in qs_last_error(): n_policies != 1 in either
+ * descriptor, differing n_envs or obs_dim, a critic with action_dim != 1, with squash_output or with finite clips (a value is neither
+ * squashed nor clipped: clip_lo <= -3e38, clip_hi >= 3e38), and whatever qs_policy_create refuses. */
+int qs_ac_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int device, qs_ac** out);
+void qs_ac_destroy(qs_ac* h);
+int qs_ac_set_stream(qs_ac* h, void* hip_stream);
+/* The two flat parameter arrays in device memory (each as in qs_policy_set_params, one row).  The handle KEEPS THE POINTERS and copies
+ * nothing: an optimiser step written into the arrays (torch.optim.Adam.step on parameters that are views of them) is what the next call reads. */
+int qs_ac_set_params(qs_ac* h, const float* actor_params, const float* critic_params);
+/* One step of collect_rollouts in one launch: `actions, values, log_probs = policy(obs)`, `clipped_actions = np.clip(actions, low, high)`
+ * and RolloutBuffer.add(obs, actions, ., ., values, log_probs).  obs [N, obs_dim], eps [N, action_dim] (required: the sample's noise, e.g. a
+ * row of one torch.randn per rollout), log_std [action_dim]; env_actions [N, action_dim] receives the CLIPPED action the environment steps
+ * with; obs_row [N, obs_dim], action_row [N, action_dim] (the UNCLIPPED action, as SB3 stores it), value_row [N], log_prob_row [N] are
+ * row t of the caller's [T, N, ...] storage.  The observation is read from global memory once. */
+int qs_ac_collect(qs_ac* h, const float* obs, const float* eps, const float* log_std, float* env_actions, float* obs_row, float* action_row,
+                  float* value_row, float* log_prob_row);
+/* policy.predict_values(obs): values_out[i] = V(obs[i]) for every i with mask[i] != 0 (mask uint8 [N], device memory; NULL = every
+ * environment); the others are not written.  collect_rollouts calls it for the last observation of a rollout. */
+int qs_ac_values(qs_ac* h, const float* obs, const uint8_t* mask_or_null, float* values_out);
+/* collect_rollouts' time-limit bootstrap (`rewards[idx] += gamma * policy.predict_values(terminal_observation)` where
+ * infos[idx]["TimeLimit.truncated"]): rewards_inout[i] = fmaf(gamma, V(terminal_obs[i]), rewards_inout[i]) where truncated[i] != 0; the
+ * others are not touched.  terminal_obs [N, obs_dim] (QS_INFO_TERMINAL_OBS, normalised by qs_norm_step's term_obs under VecNormalize). */
+int qs_ac_bootstrap(qs_ac* h, const float* terminal_obs, const uint8_t* truncated, float gamma, float* rewards_inout);
+/* RolloutBuffer.compute_returns_and_advantage(last_values, dones) as one launch, one lane per environment.  Arrays [T][N] float32 in
+ * device memory: rewards, values, episode_starts (0 or 1), advantages and returns (outputs); last_values [N], last_dones [N] uint8.  Per
+ * environment, t = T-1 ... 0:  nnt = 1 - (t == T-1 ? last_done : episode_start[t+1]);  nv = (t == T-1 ? last_value : value[t+1]);
+ * delta = fmaf(gamma * nnt, nv, reward[t]) - value[t];  gae = fmaf(gamma * lambda * nnt, gae, delta);  advantage[t] = gae;
+ * return[t] = gae + value[t].  Needs no handle: on `hip_stream` (a hipStream_t, NULL = the null stream) of the current device. */
+int qs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const uint8_t* last_dones, int T, int N,
+           float gamma, float lambda, float* advantages, float* returns, void* hip_stream);
+
 const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
-#define QS_ABI_VERSION 8
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+#define QS_ABI_VERSION 9
 int qs_abi_version(void);
 
 #ifdef __cplusplus

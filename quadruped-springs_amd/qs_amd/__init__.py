@@ -17,6 +17,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch / a GP
     if name == "DevicePolicy":
         from .policy import DevicePolicy
         return DevicePolicy
+    if name in ("DeviceActorCritic", "DeviceRolloutBuffer", "DevicePPO", "ppo_loss"):
+        from . import ppo
+        return getattr(ppo, name)
     if name == "ShardedVecEnv":
         from .sharded import ShardedVecEnv
         return ShardedVecEnv

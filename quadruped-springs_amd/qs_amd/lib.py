@@ -9,7 +9,8 @@ from .config import QsConfig
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QS_LIB_PATH") or os.path.join(_HERE, "libqs_hip.so")   # QS_LIB_PATH: kernel experiments (another build of the same ABI)
 
-ABI_VERSION = 8   # QS_ABI_VERSION of include/qs_amd.h this file was written against
+ABI_VERSION = 8   # the last QS_ABI_VERSION that changed a struct or an existing entry point: the Structures below are that version's layouts
+ABI_LIBRARY = 9   # QS_ABI_VERSION of include/qs_amd.h this file was written against, the number load() demands of the library (9 added entries only)
 
 EXPORTS = (
     "qs_create", "qs_destroy", "qs_set_stream", "qs_reset", "qs_reset_to", "qs_get_obs", "qs_step", "qs_step_fused", "qs_get_state", "qs_set_state",
@@ -18,6 +19,7 @@ EXPORTS = (
     "qs_norm_create", "qs_norm_destroy", "qs_norm_dims", "qs_norm_set_stream", "qs_norm_set_stats", "qs_norm_get_stats", "qs_norm_reset", "qs_norm_step",
     "qs_norm_step_io", "qs_host_set_norm",
     "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
+    "qs_ac_create", "qs_ac_destroy", "qs_ac_set_stream", "qs_ac_set_params", "qs_ac_collect", "qs_ac_values", "qs_ac_bootstrap", "qs_gae",
 )
 
 
@@ -124,12 +126,22 @@ def load():
         lib.qs_policy_param_count.argtypes = [vp]
         lib.qs_policy_set_params.argtypes = [vp, vp]
         lib.qs_policy_act.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "qs_ac_create"):   # (ABI 9)
+        lib.qs_ac_create.argtypes = [C.POINTER(QsPolicyDesc), C.POINTER(QsPolicyDesc), i32, C.POINTER(vp)]
+        lib.qs_ac_destroy.argtypes = [vp]
+        lib.qs_ac_destroy.restype = None
+        lib.qs_ac_set_stream.argtypes = [vp, vp]
+        lib.qs_ac_set_params.argtypes = [vp, vp, vp]
+        lib.qs_ac_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.qs_ac_values.argtypes = [vp, vp, vp, vp]
+        lib.qs_ac_bootstrap.argtypes = [vp, vp, vp, f32, vp]
+        lib.qs_gae.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)
-    if os.environ.get("QS_ALLOW_ABI_MISMATCH") != "1" and (not hasattr(lib, "qs_abi_version") or lib.qs_abi_version() != ABI_VERSION):
+    if os.environ.get("QS_ALLOW_ABI_MISMATCH") != "1" and (not hasattr(lib, "qs_abi_version") or lib.qs_abi_version() != ABI_LIBRARY):
         have = lib.qs_abi_version() if hasattr(lib, "qs_abi_version") else "none (a library of round 4 or earlier)"
-        raise RuntimeError(f"{LIB_PATH} speaks ABI {have}, this binding was written against ABI {ABI_VERSION} of include/qs_amd.h: rebuild it "
+        raise RuntimeError(f"{LIB_PATH} speaks ABI {have}, this binding was written against ABI {ABI_LIBRARY} of include/qs_amd.h: rebuild it "
                            "(python quadruped-springs_amd/build.py --force)")
     _lib = lib
     return lib

@@ -43,12 +43,23 @@ class DeviceVecNormalize:
         _lib.check(self.lib.qs_norm_reset(self.h, self._p(obs), int(self.training), int(self.norm_obs)))
         return obs
 
-    def step_tensor(self, actions):
+    def step_tensor(self, actions, terminal_obs=None):
         """-> (obs, rew, done, truncated): normalised in place in the environment's reused buffers; the raw values of this step
-        stay in `old_obs` / `old_reward` (VecNormalize.get_original_obs / get_original_reward)."""
+        stay in `old_obs` / `old_reward` (VecNormalize.get_original_obs / get_original_reward).  terminal_obs: a float32 [N, obs_dim]
+        tensor on the device that receives the step's terminal observations (get_info("terminal_obs")) normalised with this step's
+        statistics, as VecNormalize.step_wait normalises infos[i]["terminal_observation"]."""
         obs, rew, done, trunc = self.venv.step_tensor(actions)
+        p_term = None
+        if terminal_obs is not None:
+            t = self.torch
+            if (terminal_obs.dtype, terminal_obs.device, tuple(terminal_obs.shape)) != (t.float32, self.device, (self.num_envs, self.obs_dim)) or \
+                    not terminal_obs.is_contiguous():
+                raise ValueError(f"terminal_obs must be a contiguous float32 tensor of shape {(self.num_envs, self.obs_dim)} on {self.device}")
+            from .vec_env import INFO
+            p_term = self._p(terminal_obs)
+            _lib.check(self.lib.qs_get_info(self.venv.h, INFO["terminal_obs"], p_term))      # (on the stream venv.step_tensor has just set)
         self._stream()
-        _lib.check(self.lib.qs_norm_step(self.h, self._p(obs), self._p(rew), self._p(done), None, int(self.training), int(self.norm_obs),
+        _lib.check(self.lib.qs_norm_step(self.h, self._p(obs), self._p(rew), self._p(done), p_term, int(self.training), int(self.norm_obs),
                                          int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
         return obs, rew, done, trunc
 
