@@ -206,7 +206,8 @@ int qs_get_state(qs_handle* h, float* state /*[N,37]*/);
  * force F and torque tau, acting at the trunk's centre of mass (its inertial origin), on the next `substeps` physics substeps each masked
  * environment steps -- counted on the device, across env-step boundaries.  QS_FRAME_WORLD: the vectors are fixed in the world frame;
  * QS_FRAME_LINK: fixed to the trunk, turning with it.  Setting a push again replaces the earlier one; substeps = 0 cancels it; a reset of the
- * environment (auto-reset in a step, qs_reset, qs_reset_to) cancels it; qs_set_state keeps it; settles never see it.  pybullet clears external
+ * environment (auto-reset in a step, qs_reset, qs_reset_to) cancels it, and so does the step in which its episode ends (with or without auto-reset: the
+ * environment has to be reset before it steps again); qs_set_state keeps it; settles never see it.  pybullet clears external
  * forces after every stepSimulation: the reference's apply_external_force is substeps = 1, QS_FRAME_LINK, tau = 0.
  * Device pointers, stream-ordered, no host synchronisation: mask NULL = every environment, wrench [N,6] (F, tau), substeps [N].  Fails for an
  * unknown frame.  A selected row with a negative duration or a non-finite value is not taken (the environment keeps its push); as checking

@@ -25,10 +25,19 @@ def build(force=False):
     return targets
 
 
-class Oracle:
-    """Batched env on the CPU oracle.  `cfg` is a qs_amd.config.QsConfig (same layout as qso_config)."""
+class QsoRack(C.Structure):
+    """qso_rack (oracle/qso.h)"""
+    _fields_ = [("on", C.c_int32), ("anchor_pos", C.c_float * 3), ("anchor_quat", C.c_float * 4)]
 
-    def __init__(self, cfg, precision="f64"):
+
+FRAMES = {"link": 1, "world": 2, 1: 1, 2: 2}
+
+
+class Oracle:
+    """Batched env on the CPU oracle.  `cfg` is a qs_amd.config.QsConfig (same layout as qso_config).  rack: None = no rack; True = the
+    reference's anchor ([0, 0, 1], level); an anchor (position 3, quaternion xyzw 4); or meta["rack"] of qs_amd.config.build_config."""
+
+    def __init__(self, cfg, precision="f64", rack=None):
         build()
         self.real = np.float64 if precision == "f64" else np.float32
         self._creal = C.c_double if precision == "f64" else C.c_float
@@ -39,7 +48,15 @@ class Oracle:
         self.cfg = cfg
         self.n, self.d, self.o = cfg.n_envs, cfg.action_dim, cfg.obs_dim
         self.h = C.c_void_p()
-        self._check(self.lib.qso_create(C.byref(cfg), C.byref(self.h)))
+        if isinstance(rack, dict):
+            rack = np.concatenate([rack["pos"], rack["quat"]]) if rack["on"] else None
+        self.on_rack = rack is not None and rack is not False
+        if self.on_rack:
+            a = np.array([0, 0, 1, 0, 0, 0, 1], np.float32) if rack is True else np.asarray(rack, np.float32).reshape(7)
+            r = QsoRack(1, (C.c_float * 3)(*a[:3].tolist()), (C.c_float * 4)(*a[3:].tolist()))
+            self._check(self.lib.qso_create_ex(C.byref(cfg), C.byref(r), C.byref(self.h)))
+        else:
+            self._check(self.lib.qso_create(C.byref(cfg), C.byref(self.h)))
 
     def _check(self, rc):
         if rc != 0:
@@ -103,7 +120,19 @@ class Oracle:
     def restore(self, buf):
         self._check(self.lib.qso_restore(self.h, buf))
 
-    _INFO_DIM = {0: 4, 1: 4, 2: 12, 3: 12, 4: 48, 5: 1, 6: 24, 7: 4, 8: 12, 10: 4}
+    def set_external_wrench(self, wrench, substeps, frame="world", mask=None):
+        """qso_set_external_wrench: wrench [N, 6] or [6] (F, tau), substeps [N] or a scalar, frame "world" / "link" (or 2 / 1)"""
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(wrench, self.real), (self.n, 6)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(substeps, np.int32), (self.n,)))
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        self._check(self.lib.qso_set_external_wrench(self.h, None if m is None else self._p(m), self._p(w), self._p(k), FRAMES.get(frame, -1)))
+
+    def set_rack(self, hung, mask=None):
+        """release (hung False) or hang again the masked environments (None = all) for the rest of their episode"""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        self._check(self.lib.qso_set_rack(self.h, None if m is None else self._p(m), int(bool(hung))))
+
+    _INFO_DIM = {0: 4, 1: 4, 2: 12, 3: 12, 4: 48, 5: 1, 6: 24, 7: 4, 8: 12, 10: 4, 14: 8, 15: 8}
 
     def get_info(self, which):
         dim = self.o if which == 9 else self._INFO_DIM[which]
@@ -162,6 +191,12 @@ class Oracle:
         df = np.zeros((max_n, 2), self.real)
         n = self.lib.qso_get_contacts(self.h, int(env), self._p(ids), self._p(df), max_n)
         return [(int(a), int(b), int(c), int(d), float(x), float(f)) for (a, b, c, d), (x, f) in zip(ids[:min(n, max_n)], df[:min(n, max_n)])]
+
+    def foot_wrench(self):
+        """[N, 4, 6]: each foot's contact force of the last substep (world, friction included) and the point of the foot sphere it acts at"""
+        out = np.zeros((self.n, 4, 6), self.real)
+        self._check(self.lib.qso_get_foot_wrench(self.h, self._p(out)))
+        return out
 
     def boxes_overlap(self, ca, Ra, ha, cb, Rb, hb):
         args = [np.ascontiguousarray(x, self.real) for x in (ca, Ra, ha, cb, Rb, hb)]

@@ -535,7 +535,8 @@ static void add_noise(const qso_config* cfg, qso_env* e, int env_id, float* obs)
 }
 
 /* ------------------------------------------------------------------ reset / step */
-static void apply_and_step_mode(const qso_config* cfg, qso_env* e, const real* cmd, real g, int settling) {
+static void apply_and_step_mode(const qso_handle* h, qso_env* e, const real* cmd, int settling) {
+    const qso_config* cfg = &h->cfg;
     /* quadruped.py:288-320 then gym_env.py:218-219.  settling: control_interface/utils.py:7-31 switches the motor model to "PD"
        for the settle of a reset, also when the environment itself is driven by raw torques */
     real tau[12];
@@ -546,9 +547,14 @@ static void apply_and_step_mode(const qso_config* cfg, qso_env* e, const real* c
     if (cfg->enable_springs) qso_spring_torque(e->k, e->b, e->rest, e->s.q, e->s.qd, e->tau_spring);
     else memset(e->tau_spring, 0, sizeof(e->tau_spring));
     for (int i = 0; i < 12; i++) tau[i] = e->tau_pd[i] + e->tau_spring[i];
-    qso_physics_substep(cfg, e, tau, g);
+    if (settling) {   /* a settle substep is not one of the environment's own: it never sees the push, and does not count it down */
+        real anchor[7];
+        const int held = h->rack_on && e->hung;
+        if (held) { memcpy(anchor, h->rack_pos, 3 * sizeof(real)); memcpy(anchor + 3, h->rack_quat, 4 * sizeof(real)); }
+        qso_physics_substep_ext(cfg, e, tau, h->gravity, NULL, 0, held ? anchor : NULL);
+    } else qso_env_substep(h, e, tau);
 }
-static void apply_and_step(const qso_config* cfg, qso_env* e, const real* cmd, real g) { apply_and_step_mode(cfg, e, cmd, g, 0); }
+static void apply_and_step(const qso_handle* h, qso_env* e, const real* cmd) { apply_and_step_mode(h, e, cmd, 0); }
 
 static void randomize(const qso_config* cfg, qso_env* e, int env_id) {
     if ((cfg->randomizer_flags & QSO_RAND_KEEP) && e->episode >= 0) return;
@@ -599,6 +605,11 @@ static void reset_env_to(qso_handle* h, int i, const real* st37) {
     /* quadruped.py:487-519, configs:23,26,31-36 */
     memset(&e->s, 0, sizeof(e->s));
     e->s.pos[2] = (real)0.32; e->s.quat[3] = 1;
+    memset(&e->push, 0, sizeof(e->push));   /* every reset cancels the push ... */
+    e->hung = h->rack_on; memset(e->rack_lam, 0, sizeof(e->rack_lam));   /* ... and hangs the robot again */
+    if (h->rack_on) {   /* _GetDefaultInitPosition (quadruped.py:86-96): INIT_RACK_POSITION, here the anchor */
+        memcpy(e->s.pos, h->rack_pos, sizeof(e->s.pos)); memcpy(e->s.quat, h->rack_quat, sizeof(e->s.quat));
+    }
     for (int L = 0; L < 4; L++) { e->s.q[3 * L] = 0; e->s.q[3 * L + 1] = PI / 4; e->s.q[3 * L + 2] = -PI / 2; }
     memset(e->warm, 0, sizeof(e->warm)); memset(e->foot_force, 0, sizeof(e->foot_force));
     memset(e->foot_contact, 0, sizeof(e->foot_contact)); e->n_invalid = 0;
@@ -611,7 +622,7 @@ static void reset_env_to(qso_handle* h, int i, const real* st37) {
         qso_block_place(e);   /* (the reference leaves the block at the spawn pose and lets the constraint drag it; here it moves with the robot) */
     } else {
         real cmd[12]; for (int k = 0; k < 12; k++) cmd[k] = cfg->settle_cmd[k];
-        for (int n = 0; n < cfg->settle_steps; n++) apply_and_step_mode(cfg, e, cmd, h->gravity, 1);
+        for (int n = 0; n < cfg->settle_steps; n++) apply_and_step_mode(h, e, cmd, 1);
         for (int k = 0; k < 12; k++) e->last_action[k] = k < cfg->action_dim ? (real)cfg->settle_action[k] : 0;
     }
     if (cfg->action_space_mode == QSO_ACT_CPG) { /* hopf_network.py:62-63: r ~ 0.1 U(0,1), theta = PHI[0,:] */
@@ -629,8 +640,18 @@ static void reset_env_to(qso_handle* h, int i, const real* st37) {
     for (int k = 0; k < d; k++) { e->xhist[k] = e->xhist[d + k] = e->last_action[k]; e->yhist[k] = e->yhist[d + k] = e->last_action[k]; }
 }
 
-int qso_create(const qso_config* cfg, qso_handle** out) {
+int qso_create(const qso_config* cfg, qso_handle** out) { return qso_create_ex(cfg, NULL, out); }
+int qso_create_ex(const qso_config* cfg, const qso_rack* rack, qso_handle** out) {
     if (!cfg || !out) FAIL("null argument");
+    real rq[4] = {0, 0, 0, 1};
+    if (rack && rack->on) {
+        if (cfg->payload_soft) FAIL("the rack is not implemented together with payload_soft");
+        real n2 = 0;
+        for (int k = 0; k < 4; k++) { rq[k] = rack->anchor_quat[k]; n2 += rq[k] * rq[k]; }
+        for (int k = 0; k < 3; k++) if (!isfinite(rack->anchor_pos[k])) FAIL("the rack's anchor position is not finite");
+        if (!isfinite(n2) || !(n2 > 0)) FAIL("the rack's anchor quaternion is zero or not finite");
+        for (int k = 0; k < 4; k++) rq[k] /= sqrt(n2);
+    }
     if (cfg->n_envs <= 0) FAIL("n_envs must be positive");
     if (cfg->obs_dim > QSO_MAX_OBS || cfg->n_sensors > QSO_MAX_SENSORS) FAIL("observation too large");
     if (cfg->motor_control_mode == QSO_MOTOR_TORQUE && cfg->rl_interface) FAIL("TORQUE mode not implemented for the RL interface");
@@ -638,15 +659,45 @@ int qso_create(const qso_config* cfg, qso_handle** out) {
     if (od != cfg->obs_dim) FAIL("obs_dim %d does not match sensor bundle (%d)", cfg->obs_dim, od);
     qso_handle* h = (qso_handle*)calloc(1, sizeof(*h));
     h->cfg = *cfg; h->gravity = cfg->gravity;
+    if (rack && rack->on) {
+        h->rack_on = 1;
+        for (int k = 0; k < 3; k++) h->rack_pos[k] = rack->anchor_pos[k];
+        memcpy(h->rack_quat, rq, sizeof(rq));
+    }
     h->env = (qso_env*)calloc((size_t)cfg->n_envs, sizeof(qso_env));
     for (int i = 0; i < cfg->n_envs; i++) {
         qso_env* e = &h->env[i];
         e->episode = -1;
+        e->hung = h->rack_on;
         randomize(cfg, e, i); /* nominal-ish params so that physics-only calls work before the first reset */
         e->s.pos[2] = (real)0.32; e->s.quat[3] = 1;
         for (int L = 0; L < 4; L++) { e->s.q[3 * L + 1] = PI / 4; e->s.q[3 * L + 2] = -PI / 2; }
     }
     *out = h;
+    return 0;
+}
+int qso_set_rack(qso_handle* h, const uint8_t* mask, int hung) {
+    if (!h->rack_on) FAIL("qso_set_rack: the handle has no rack");
+    for (int i = 0; i < h->cfg.n_envs; i++) if (!mask || mask[i]) {
+        h->env[i].hung = hung != 0;
+        memset(h->env[i].rack_lam, 0, sizeof(h->env[i].rack_lam));   /* no substep has run under the new state yet */
+    }
+    return 0;
+}
+int qso_set_external_wrench(qso_handle* h, const uint8_t* mask, const real* wrench, const int32_t* substeps, int frame) {
+    if (frame != QSO_FRAME_LINK && frame != QSO_FRAME_WORLD) FAIL("unknown frame %d", frame);
+    if (!wrench || !substeps) FAIL("null argument");
+    int refused = -1;
+    for (int i = 0; i < h->cfg.n_envs; i++) if (!mask || mask[i]) {
+        const real* w = wrench + (size_t)i * 6;
+        int ok = substeps[i] >= 0;
+        for (int k = 0; k < 6; k++) ok = ok && isfinite(w[k]);
+        if (!ok) { if (refused < 0) refused = i; continue; }   /* the environment keeps its push */
+        qso_env* e = &h->env[i];
+        memcpy(e->push.F, w, 3 * sizeof(real)); memcpy(e->push.tau, w + 3, 3 * sizeof(real));
+        e->push.left = substeps[i]; e->push.frame = frame;
+    }
+    if (refused >= 0) FAIL("push of environment %d refused: negative duration or non-finite value", refused);
     return 0;
 }
 void qso_destroy(qso_handle* h) { if (h) { free(h->demo); free(h->env); free(h); } }
@@ -745,7 +796,7 @@ static int step_env(qso_handle* h, int i, const float* action_row, float* obs_ro
         else for (int k = 0; k < 12; k++) cmd[k] = act[k];
         for (int s = 0; s < cfg->action_repeat; s++) {
             if (cpg) cpg_command(cfg, e, cpgp, cmd);   /* the oscillators tick at the physics rate (hopf_network.py:241-289) */
-            apply_and_step(cfg, e, cmd, h->gravity); e->sim_step++;
+            apply_and_step(h, e, cmd); e->sim_step++;
             if (h->trace && i == h->trace_env) { /* monitor_state.py:66-85 */
                 real* r = h->trace + (size_t)s * QSO_TRACE_DIM;
                 r[0] = sim_time(cfg, e);
@@ -761,6 +812,7 @@ static int step_env(qso_handle* h, int i, const float* action_row, float* obs_ro
         int term = task_terminated(cfg, e);
         int dn = term || e->sim_step > cfg->max_sim_steps;
         if (dn) r += task_reward_end(cfg, e);
+        if (dn) e->push.left = 0;   /* the end of the episode cancels the push, whoever resets the environment */
         if (swapped) for (int k = 0; k < 3; k++) { e->kp[k] = kp_save[k]; e->kd[k] = kd_save[k]; }
         if (cfg->wrapper_mode == QSO_WRAP_GO_TO_REST) { e->wrap.h_old = e->wrap.h_act; e->wrap.h_act = e->s.pos[2]; }
         if (!dn && wt.landing_family) {
@@ -900,6 +952,18 @@ int qso_get_info(qso_handle* h, int which, real* out) {
         case QSO_INFO_COUNTERS: out[4 * i] = e->sim_step; out[4 * i + 1] = e->env_step; out[4 * i + 2] = e->episode; out[4 * i + 3] = e->total_steps; break;
         case QSO_INFO_LAST_ACTION: for (int k = 0; k < 12; k++) out[12 * i + k] = e->last_action[k]; break;
         case QSO_INFO_TERMINAL_OBS: for (int k = 0; k < h->cfg.obs_dim; k++) out[(size_t)i * h->cfg.obs_dim + k] = e->term_obs[k]; break;
+        case QSO_INFO_EXTERNAL_WRENCH: {
+            real* o = out + 8 * i;
+            memcpy(o, e->push.F, 3 * sizeof(real)); memcpy(o + 3, e->push.tau, 3 * sizeof(real)); o[6] = e->push.left; o[7] = e->push.frame;
+            break; }
+        case QSO_INFO_RACK: {
+            if (!h->rack_on) FAIL("QSO_INFO_RACK: the handle has no rack");
+            real* o = out + 8 * i, d2 = 0;
+            o[0] = e->hung;
+            for (int k = 0; k < 6; k++) o[1 + k] = e->rack_lam[k] / (real)h->cfg.dt;
+            for (int k = 0; k < 3; k++) d2 += (e->s.pos[k] - h->rack_pos[k]) * (e->s.pos[k] - h->rack_pos[k]);
+            o[7] = sqrt(d2);
+            break; }
         case QSO_INFO_WRAPPER: out[4 * i] = e->wrap.phase; out[4 * i + 1] = e->wrap.scripted; out[4 * i + 2] = e->wrap.timer; out[4 * i + 3] = e->wrap.end; break;
         case QSO_INFO_TASK: {
             real* o = out + 48 * i; memset(o, 0, 48 * sizeof(real));

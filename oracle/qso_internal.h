@@ -52,6 +52,7 @@ typedef struct {
     real m_trunk, m_leg[3], m_pay, r_pay[3];
     /* results of the last physics substep */
     real foot_force[4];
+    real foot_tangent[4][2];   /* friction force of each foot at the last substep along world x and y */
     int foot_contact[4];
     int n_invalid;
     /* every contact point of the last substep as getContactPoints() would list it (PyBullet ids: body 0 plane, 1 robot, 2 payload block;
@@ -67,6 +68,10 @@ typedef struct {
        the last substep and the distance between the two pivots */
     struct { real pos[3], quat[4], v[3], w[3], lam[6], gap; } blk;
     real tau_pd[NJ], tau_spring[NJ];
+    /* the push of qso_set_external_wrench: as set, in its frame; substeps it still acts on */
+    struct { real F[3], tau[3]; int left, frame; } push;
+    /* the rack: hung (1) or released (0); impulses of its six rows at the last substep */
+    int hung; real rack_lam[6];
     /* env-level */
     real last_action[12], last_filtered[12], xhist[24], yhist[24];
     int sim_step, env_step, episode;
@@ -84,18 +89,24 @@ struct qso_handle {
     real gravity;
     real* trace; int trace_env;
     float* demo; int demo_len;   /* qso_set_demo */
+    int rack_on; real rack_pos[3], rack_quat[4];   /* qso_create_ex */
 };
 
 /* qso_model.c */
 void qso_model_build(qso_model* M, const float (*unit)[6], real m_trunk, const real* m_leg3, real m_pay, const real* r_pay);
 void qso_block_place(qso_env* e);   /* puts the payload block where the fixed constraint wants it, at the base's velocity */
 extern const real QSO_TRUNK_I[6], QSO_HIP_I[6], QSO_THIGH_I[6], QSO_CALF_I[6];   /* URDF tensors (FR-leg magnitudes) */
-extern const real QSO_M_TRUNK, QSO_M_LEG[3];
+extern const real QSO_M_TRUNK, QSO_M_LEG[3], QSO_TRUNK_COM[3];
 extern const real QSO_JOINT_LO[3], QSO_JOINT_HI[3];
 
 /* qso_phys.c */
 void qso_quat_to_mat(const real* q, real R[3][3]);
 void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, real g);
+/* the same with what acts on the trunk from outside: `wrench` (NULL: none) = F 3, tau 3 at the trunk's inertial origin, in `frame`
+ * (QSO_FRAME_*); `anchor` (NULL: no rack, or released) = position 3, quaternion xyzw 4 of the rack */
+void qso_physics_substep_ext(const qso_config* cfg, qso_env* e, const real* tau, real g, const real* wrench, int frame, const real* anchor);
+/* one of the environment's own (non-settle) substeps: its push, counted down, and its rack */
+void qso_env_substep(const qso_handle* h, qso_env* e, const real* tau);
 
 /* small vector helpers */
 static inline void v3cross(const real* a, const real* b, real* c) {

@@ -7,7 +7,7 @@
 
 /* trunk :80-85 */
 const real QSO_M_TRUNK = 5.204;
-static const real TRUNK_COM[3] = {0.0223, 0.0, -0.0005};
+const real QSO_TRUNK_COM[3] = {0.0223, 0.0, -0.0005};
 const real QSO_TRUNK_I[6] = {0.0168352186, 0.0004636141, 0.0002367952, 0.0656071082, 3.6671e-05, 0.0742720659};
 /* base :55-59, imu :87-97 */
 static const real BASE_M = 0.00001, BASE_I = 1e-5;
@@ -82,7 +82,7 @@ void qso_model_build(qso_model* M, const float (*unit)[6], real m_trunk, const r
     real It[3][3]; sym6_to_mat(ut, It);
     real sc = m_trunk;
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) It[i][j] *= sc;
-    acc_add(&a, m_trunk, TRUNK_COM, It);
+    acc_add(&a, m_trunk, QSO_TRUNK_COM, It);
     memset(Idiag, 0, sizeof(Idiag)); Idiag[0][0] = Idiag[1][1] = Idiag[2][2] = IMU_I;
     acc_add(&a, IMU_M, IMU_POS, Idiag);
     if (m_pay > 0) {

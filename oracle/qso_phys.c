@@ -13,7 +13,8 @@
  *      contacts that involve a calf (self-collision rule) are counted
  *   4. constraint rows: per contact point 1 normal + 2 friction rows -- implicit cone (cfg.friction_cone, PyBullet's default: both friction
  *      rows from the same velocities, projected onto the disc of radius mu*f_n) or pyramid (|f_t| <= mu*f_n per direction) --, violated
- *      joint limits as unilateral rows, the six rows of the payload block's fixed constraint (cfg.payload_soft); projected Gauss-Seidel in
+ *      joint limits as unilateral rows, the six rows of the payload block's fixed constraint (cfg.payload_soft) or of the rack (the same
+ *      constraint against the static world); an external wrench on the trunk enters step 1 as a spatial force on body 0; projected Gauss-Seidel in
  *      Bullet's row order, at most `solver_iters` sweeps (gym_env.py:113,302) with PyBullet's residual early exit, velocity space
  *   5. semi-implicit Euler on positions (quaternion by exponential map)
  */
@@ -143,8 +144,9 @@ static void kinematics(const qso_model* M, const qso_dyn* s, phys_cache* C) {
     }
 }
 
-/* forward dynamics; acc = [alpha_b a_b qdd] (base part: spatial acceleration in base coordinates) */
-static int aba(const qso_model* M, const qso_dyn* s, const real* tau, real g, phys_cache* C, real* acc) {
+/* forward dynamics; acc = [alpha_b a_b qdd] (base part: spatial acceleration in base coordinates).  fext0 (NULL: none): an external spatial
+   force on body 0, [moment about the base origin; force] in base coordinates (Featherstone 2008, Table 9.4: p_i^A = v x* I v - f_i^x) */
+static int aba(const qso_model* M, const qso_dyn* s, const real* tau, real g, phys_cache* C, real* acc, const real* fext0) {
     real c[NB][6], pA[NB][6], u[NB], a[NB][6];
     for (int i = 0; i < NB; i++) {
         memcpy(C->IA[i], M->I6[i], sizeof(M->I6[i]));
@@ -156,6 +158,7 @@ static int aba(const qso_model* M, const qso_dyn* s, const real* tau, real g, ph
             crm(C->v[i], vJ, c[i]);
         }
     }
+    if (fext0) for (int k = 0; k < 6; k++) pA[0][k] -= fext0[k];
     for (int i = NB - 1; i >= 1; i--) {
         int p = M->parent[i], ax = M->jaxis[i];
         for (int k = 0; k < 6; k++) C->U[i][k] = C->IA[i][k][ax];
@@ -415,14 +418,27 @@ static void contact_rows(const qso_config* cfg, const qso_model* M, const phys_c
     }
 }
 
-void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, real g) {
+void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, real g) { qso_physics_substep_ext(cfg, e, tau, g, NULL, 0, NULL); }
+
+void qso_physics_substep_ext(const qso_config* cfg, qso_env* e, const real* tau, real g, const real* wrench, int frame, const real* anchor) {
     const qso_model* M = &e->model;
     qso_dyn* s = &e->s;
     phys_cache C;
     real dt = cfg->dt, cap = cfg->vel_cap;
     kinematics(M, s, &C);
     real acc[NV];
-    aba(M, s, tau, g, &C, acc);
+    real fext[6];
+    if (wrench) {
+        /* applyExternalForce(robot, trunk, F, [0,0,0], frame) (quadruped.py:338-343) plus a torque: F acts at the trunk link's inertial origin
+           c (go1.urdf:80-85), so about the base origin it has the moment c x F.  A world-frame wrench is seen from the orientation this
+           substep starts from; pybullet clears external forces after every stepSimulation, so it is applied afresh each substep. */
+        real Fb[3], Tb[3], m[3];
+        if (frame == QSO_FRAME_WORLD) { m3tv(C.R0, wrench, Fb); m3tv(C.R0, wrench + 3, Tb); }
+        else { memcpy(Fb, wrench, sizeof(Fb)); memcpy(Tb, wrench + 3, sizeof(Tb)); }
+        v3cross(QSO_TRUNK_COM, Fb, m);
+        for (int k = 0; k < 3; k++) { fext[k] = m[k] + Tb[k]; fext[3 + k] = Fb[k]; }
+    }
+    aba(M, s, tau, g, &C, acc, wrench ? fext : NULL);
 
     /* generalized velocity in base coordinates, predicted */
     real v[NV];
@@ -511,6 +527,36 @@ void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, rea
             r->lo = -bound; r->hi = bound; r->fric_of = -1;
         }
     }
+    /* the rack (quadruped.py:474-484: createConstraint(robot, -1, -1, -1, JOINT_FIXED, ..., anchor, childFrameOrientation)): the fixed
+       constraint above with the static world in the block's place -- no second body, so the rows end at the robot's 18 velocities; pivot A is
+       the base origin, pivot B the anchor */
+    int rack0 = -1;
+    memset(e->rack_lam, 0, sizeof(e->rack_lam));
+    if (anchor) {
+        real perr[3]; for (int k = 0; k < 3; k++) perr[k] = s->pos[k] - anchor[k];
+        const real* qa = s->quat; const real* qb = anchor + 3;
+        real qe[4] = {qa[3] * -qb[0] + qa[0] * qb[3] + qa[1] * -qb[2] - qa[2] * -qb[1],
+                      qa[3] * -qb[1] - qa[0] * -qb[2] + qa[1] * qb[3] + qa[2] * -qb[0],
+                      qa[3] * -qb[2] + qa[0] * -qb[1] - qa[1] * -qb[0] + qa[2] * qb[3],
+                      qa[3] * qb[3] - qa[0] * -qb[0] - qa[1] * -qb[1] - qa[2] * -qb[2]};
+        real sg = qe[3] < 0 ? -2 : 2, aerr[3] = {sg * qe[0], sg * qe[1], sg * qe[2]};
+        real bound = (real)500.0 * dt;
+        rack0 = nlim;
+        for (int k = 0; k < 6; k++) {
+            row* r = &lim[nlim++];
+            memset(r, 0, sizeof(*r));
+            real ax[3] = {k % 3 == 0, k % 3 == 1, k % 3 == 2}, ab[3];
+            m3tv(C.R0, ax, ab);
+            for (int i = 0; i < 3; i++) r->J[(k < 3 ? 3 : 0) + i] = ab[i];
+            minv_apply(M, &C, r->J, r->W);
+            real d = 0; for (int i = 0; i < NV; i++) d += r->J[i] * r->W[i];
+            r->dinv = 1 / d;
+            real rel = 0; for (int i = 0; i < NV; i++) rel += r->J[i] * v[i];
+            real err = k < 3 ? perr[k] : aerr[k - 3];
+            r->rhs = (-err * cfg->joint_erp / dt - rel) * r->dinv;
+            r->lo = -bound; r->hi = bound; r->fric_of = -1;
+        }
+    }
     /* contacts, leg by leg: the foot, then (cfg->body_contacts) up to two more support points of the leg -- the lowest of
        {the trunk corner on the leg's side, hip housing, the two ends of the thigh box, knee end of the calf box} within contact range */
     for (int L = 0; L < 4; L++) {
@@ -518,7 +564,7 @@ void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, rea
         real c3[3]; m3v(C.Rw[ic], FOOT_OFF, c3);
         real centre[3] = {C.ow[ic][0] + c3[0], C.ow[ic][1] + c3[1], C.ow[ic][2] + c3[2]};
         real dist = centre[2] - FOOT_R;
-        e->foot_contact[L] = 0; e->foot_force[L] = 0;
+        e->foot_contact[L] = 0; e->foot_force[L] = 0; e->foot_tangent[L][0] = e->foot_tangent[L][1] = 0;
         if (!(dist < THR_FOOT)) e->warm[L] = 0;
         else {
             e->foot_contact[L] = 1;
@@ -674,6 +720,8 @@ void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, rea
     for (int i = 0; i < nn; i++) {
         if (nor_foot[i] >= 0) {
             e->foot_force[nor_foot[i]] = nor[i].lam / dt;
+            e->foot_tangent[nor_foot[i]][0] = fr[2 * i + 1].lam / dt;   /* t2 = +x */
+            e->foot_tangent[nor_foot[i]][1] = -fr[2 * i].lam / dt;      /* t1 = -y */
             e->warm[nor_foot[i]] = nor[i].lam;
             e->contacts[nor_contact[i]].force = nor[i].lam / dt;
         } else {   /* support point of another link: its force goes to that link's entry of the contact list */
@@ -682,6 +730,7 @@ void qso_physics_substep(const qso_config* cfg, qso_env* e, const real* tau, rea
                 if (e->contacts[c].body_a == 1 && e->contacts[c].body_b == 0 && e->contacts[c].link_a == -1 - nor_contact[i]) { e->contacts[c].force += nor[i].lam / dt; break; }
         }
     }
+    if (rack0 >= 0) for (int k = 0; k < 6; k++) e->rack_lam[k] = lim[rack0 + k].lam;
     if (fixed0 >= 0) {
         for (int k = 0; k < 6; k++) e->blk.lam[k] = lim[fixed0 + k].lam;
         for (int k = 0; k < 3; k++) { e->blk.w[k] += dv[18 + k]; e->blk.v[k] += dv[21 + k]; }
@@ -785,10 +834,18 @@ int qso_phys_crba_rnea(qso_handle* h, int env, real* H, real* C) {
 }
 int qso_phys_aba(qso_handle* h, int env, const real* tau, real* acc) {
     phys_cache C; kinematics(&h->env[env].model, &h->env[env].s, &C);
-    return aba(&h->env[env].model, &h->env[env].s, tau, h->gravity, &C, acc);
+    return aba(&h->env[env].model, &h->env[env].s, tau, h->gravity, &C, acc, NULL);
+}
+void qso_env_substep(const qso_handle* h, qso_env* e, const real* tau) {
+    real w[6], anchor[7];
+    const int pushed = e->push.left > 0;
+    if (pushed) { memcpy(w, e->push.F, 3 * sizeof(real)); memcpy(w + 3, e->push.tau, 3 * sizeof(real)); e->push.left--; }
+    const int held = h->rack_on && e->hung;
+    if (held) { memcpy(anchor, h->rack_pos, 3 * sizeof(real)); memcpy(anchor + 3, h->rack_quat, 4 * sizeof(real)); }
+    qso_physics_substep_ext(&h->cfg, e, tau, h->gravity, pushed ? w : NULL, e->push.frame, held ? anchor : NULL);
 }
 int qso_phys_step(qso_handle* h, int env, const real* tau) {
-    qso_physics_substep(&h->cfg, &h->env[env], tau, h->gravity);
+    qso_env_substep(h, &h->env[env], tau);
     return 0;
 }
 int qso_phys_set_gravity(qso_handle* h, real g) { h->gravity = g; return 0; }
@@ -802,6 +859,20 @@ int qso_get_block(qso_handle* h, real* out /*[N,20]: pos3 quat4 v3 w3 lam6 gap*/
         const qso_env* e = &h->env[i]; real* o = out + 20 * i;
         memcpy(o, e->blk.pos, 3 * sizeof(real)); memcpy(o + 3, e->blk.quat, 4 * sizeof(real)); memcpy(o + 7, e->blk.v, 3 * sizeof(real));
         memcpy(o + 10, e->blk.w, 3 * sizeof(real)); memcpy(o + 13, e->blk.lam, 6 * sizeof(real)); o[19] = e->blk.gap;
+    }
+    return 0;
+}
+int qso_get_foot_wrench(qso_handle* h, real* out /*[N,4,6]*/) {
+    for (int i = 0; i < h->cfg.n_envs; i++) {
+        const qso_env* e = &h->env[i];
+        phys_cache C; kinematics(&e->model, &e->s, &C);
+        for (int L = 0; L < 4; L++) {
+            real* o = out + 24 * i + 6 * L, c3[3];
+            m3v(C.Rw[3 + 3 * L], FOOT_OFF, c3);
+            o[0] = e->foot_tangent[L][0]; o[1] = e->foot_tangent[L][1]; o[2] = e->foot_force[L];
+            for (int k = 0; k < 3; k++) o[3 + k] = C.ow[3 + 3 * L][k] + c3[k];
+            o[5] -= FOOT_R;
+        }
     }
     return 0;
 }

@@ -1,6 +1,8 @@
 """External pushes on the trunk (qs_set_external_wrench) in the host emulation (tests/emu/qs_emu_step.cpp): the velocity change of one
 substep against the float64 mass matrix of the oracle, the common-path build's hand-over under a push against the full build bit for bit,
-a zero-duration push against the push-free step, and the bindings' refusals.  No GPU."""
+a zero-duration push against the push-free step, the bindings' refusals, and the schedules of push_rack_cases.py -- pushed on the ground
+under PD, toppled, a duration that crosses six env steps -- against the float64 oracle under the yardstick (the CPU twins of
+test_gpu_push.py).  No GPU."""
 import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation
@@ -180,6 +182,36 @@ def test_push_acts_on_exactly_its_substeps(variant):
     step_push(emus[3], act, rows[3], variant)
     step_push(emus[2], act, row(1), variant)
     assert_bitwise(emus[2].records(), emus[3].records(), "3 substeps at once vs 2 + 1")
+
+
+def emu_device(variant):
+    """make_device of push_rack_cases.run: the emulation through the builds of step kernel `variant` (0 = the full build alone)"""
+    import yardstick as Y
+
+    def make(cfg, meta):
+        rk = meta["rack"]
+        dev = Y.EmuDevice(Emu(cfg, rack=np.concatenate([rk["pos"], rk["quat"]]) if rk["on"] else None), variant)
+        dev.reset(np.ones(cfg.n_envs, np.uint8))
+        return dev
+    return make
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("case", ["ground_cone", "ground_pyramid", "topple", "repeat4"])
+def test_pushes_against_the_oracle(case, variant):
+    """push_rack_cases.PUSH_CASES through yardstick.resynced_parity with the emulation as the device: every step from the oracle's state,
+    strict (pose 5e-6, base velocity 5e-4, q 2e-5, qd 5e-3) where the step map is smooth, tolerance + 5 x |oracle32 - oracle64| where a
+    non-foot link touched the ground; the remaining-substeps column equal on both oracle builds and the emulation before and after every
+    step; the coverage the case exists for.  The full build and both hand-over variants."""
+    import push_rack_cases as P
+    P.check(P.run(case, P.PUSH_CASES, emu_device(variant)), f"test_emu_push[{case}-{variant}]", "emulation")
+
+
+@pytest.mark.parametrize("case", ["ground_cone", "ground_pyramid", "topple", "repeat4"])
+def test_float32_oracle_meets_the_push_schedules(case):
+    """the oracle's own float32 build as the device: inside the same bounds, and the coverage counts are met by the oracles alone"""
+    import push_rack_cases as P
+    P.check(P.run(case, P.PUSH_CASES, P.OracleDevice), f"test_emu_push[{case}-oracle32]", "oracle32")
 
 
 class _Stub:

@@ -1,7 +1,9 @@
 """The rack (on_rack=True: qs_create_ex with a qs_rack) in the host emulation (tests/emu/qs_emu_step.cpp): the velocity change of one substep
 against a float64 PGS of the six rows through the oracle's mass matrix, the reported reaction, the common-path build's hand-over to the full
 build bit for bit with a joint at its stop, the many-rows solve's rack rows against tests/rare_ref.py, a static hang after a reset, a
-release and a re-hang, and the bindings' refusals.  No GPU."""
+release and a re-hang, the bindings' refusals, and the schedules of push_rack_cases.py -- hung under PD, hung on a low anchor with the
+feet on the floor, released and hung again while falling, joints at their stops -- against the float64 oracle under the yardstick, the
+rack's reaction included (the CPU twins of test_gpu_rack.py).  No GPU."""
 import ctypes as C
 
 import numpy as np
@@ -239,6 +241,42 @@ def test_released_robot_falls_and_rehung_robot_is_pulled_back():
     assert gap[-1] < 2e-3 and gap[-20:].max() < 2e-3, gap[-20:]
     assert np.abs(rack_info(e)[0, 1:7]).max() < 500.0                # back at rest: the bound no longer binds
     assert np.degrees(Rotation.from_quat(e.get_state()[0, 3:7].astype(np.float64)).magnitude()) < 0.5
+
+
+RACK_TWINS = ["hung_cone", "hung_pyramid", "low_anchor", "low_anchor_sweeps3", "rehang", "stops"]
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("case", RACK_TWINS)
+def test_rack_against_the_oracle(case, variant):
+    """push_rack_cases.RACK_CASES through yardstick.resynced_parity with the emulation as the device: state, observation, reward, torques,
+    foot forces and the rack's reaction (force: 0.5 N + 2 %; torque: yardstick.RACK_FIELDS) strictly where the step map is smooth, under
+    the spread rule where the rack's bound binds in either oracle build or a link is on the ground; hung flags equal before and after
+    every step; the coverage the case exists for.  The full build and both hand-over variants."""
+    import push_rack_cases as P
+    from test_emu_push import emu_device
+    P.check(P.run(case, P.RACK_CASES, emu_device(variant)), f"test_emu_rack[{case}-{variant}]", "emulation")
+
+
+@pytest.mark.parametrize("case", RACK_TWINS)
+def test_float32_oracle_meets_the_rack_schedules(case):
+    import push_rack_cases as P
+    P.check(P.run(case, P.RACK_CASES, P.OracleDevice), f"test_emu_rack[{case}-oracle32]", "oracle32")
+
+
+def test_rack_torque_floor_is_the_measured_one():
+    """yardstick.RACK_FIELDS' floor for the reaction's torque is FACTOR x the 99th percentile of |oracle32 - oracle64| over the smooth hung
+    rows of the rack schedules, as written next to it: measured again here, it lies within a factor 1.5 of the recorded figure"""
+    import push_rack_cases as P
+    import yardstick as Y
+    pool = []
+    for case in RACK_TWINS:
+        pool += P.run(case, P.RACK_CASES, P.OracleDevice)["rack_own_smooth"]["rack_torque"]
+    p50, p90, p99 = Y.percentiles(pool)
+    print("rack torque |oracle32 - oracle64| over", len(pool), "smooth rows: p50 / p90 / p99", p50, p90, p99)
+    assert len(pool) >= 1000
+    assert Y.RACK_TORQUE_OWN["p99"] / 1.5 <= p99 <= Y.RACK_TORQUE_OWN["p99"] * 1.5, (p99, Y.RACK_TORQUE_OWN)
+    assert Y.RACK_FIELDS["rack_torque"] == (3, Y.FACTOR * Y.RACK_TORQUE_OWN["p99"])
 
 
 # ---- bindings (no device needed)

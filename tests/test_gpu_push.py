@@ -1,6 +1,8 @@
 """External pushes on the trunk (qs_set_external_wrench, QuadrupedVecEnv.apply_external_force) on the device: the velocity change of
 one substep against the float64 mass matrix, the duration counted across env steps, independence of environments without a push,
-both step kernels, resets, the host / fused paths and the single-environment drop-in."""
+both step kernels, resets, the host / fused paths and the single-environment drop-in; and the schedules of push_rack_cases.py -- pushed on
+the ground under PD with springs and the filter, toppled by a push, a duration that crosses six env steps -- held to the float64 oracle
+under the yardstick (tests/yardstick.py resynced_parity)."""
 import os
 
 import numpy as np
@@ -292,3 +294,28 @@ def test_refused_device_rows_are_reported(torch_cuda):
     v.apply_external_force(F.nan_to_num(), substeps=k)
     with pytest.raises(RuntimeError, match="refused the row of environment 7"):
         v.counter(0)
+
+
+def vec_device(cfg, meta):
+    """make_device of push_rack_cases.run: a device handle for the case's configuration (from_config takes meta["rack"]), reset"""
+    import yardstick as Y
+    from qs_amd.vec_env import QuadrupedVecEnv
+    v = QuadrupedVecEnv.from_config(cfg, meta)
+    v.reset()
+    return Y.VecEnvDevice(v)
+
+
+@pytest.mark.parametrize("case, step_kernel", [("ground_cone", "1"), ("ground_cone", "2"), ("ground_pyramid", None), ("topple", None), ("repeat4", None)])
+def test_pushes_against_the_oracle(torch_cuda, monkeypatch, case, step_kernel):
+    """push_rack_cases.PUSH_CASES on the device (n = 16, one wave), every step from the oracle's state: strict (pose 5e-6, base velocity
+    5e-4, q 2e-5, qd 5e-3; torques, foot forces, observation, reward) where the step map is smooth, tolerance + 5 x |oracle32 - oracle64|
+    where a non-foot link touched the ground, the impact rows' 90th and 99th percentile within tolerance + 2 x the float32 oracle's own;
+    the remaining-substeps column equal on both oracle builds and the device before and after every step.
+    ground_*: default task, a push of +-150 N / +-8 N m every 3rd step for 0, 1, 5 or 25 substeps, world and link frame in turn (at least
+    100 compared env-steps with a push active and a foot in contact), cone under either step kernel, pyramid.  topple: 300 - 600 N
+    sideways with a roll torque for 60 substeps on half of the environments (at least 30 impact rows).  repeat4: action_repeat = 4,
+    time_step = 0.0025, pushes of 25 substeps.  The CPU twins are tests/test_emu_push.py::test_pushes_against_the_oracle."""
+    import push_rack_cases as P
+    if step_kernel:
+        monkeypatch.setenv("QS_STEP_VARIANT", step_kernel)
+    P.check(P.run(case, P.PUSH_CASES, vec_device), f"test_gpu_push[{case}-{step_kernel}]")

@@ -1,6 +1,8 @@
 """The rack (on_rack=True) on the device: the step of hung, released and re-hung robots with either step kernel, bit for bit, and against
 the host emulation, released wave-mates leave the hung ones' bits alone, a released robot's fall against the oracle, look-ahead resets against
-in-place ones, auto-reset and seed() hang the robot again, the single-environment drop-in, and set_rack never waits for the device."""
+in-place ones, auto-reset and seed() hang the robot again, the single-environment drop-in, set_rack never waits for the device; and the
+schedules of push_rack_cases.py -- hung under PD, hung on a low anchor with the feet on the floor, released and hung again while falling,
+joints at their stops -- held to the float64 oracle under the yardstick, the rack's reaction included."""
 import numpy as np
 import pytest
 
@@ -50,9 +52,14 @@ def test_both_step_kernels_agree_and_follow_the_emulation(torch_cuda, monkeypatc
         v.seed(int(v.cfg.seed))                  # (a handle with the edited configuration: seed() recreates it, keeping the rack)
         vs.append(v)
     e = Emu(vs[0].cfg)
+    import yardstick as Y
+    from oracle.qso import Oracle
+    o, o32 = Oracle(vs[0].cfg, rack=vs[0].meta["rack"]), Oracle(vs[0].cfg, "f32", rack=vs[0].meta["rack"])
+    base = Y.STATE_GROUPS[:2]                      # pose, base velocity: the columns the line against the emulation compares
     for v in vs:
         v.reset_tensor()
     reset_rack(e)
+    o.reset(); o32.reset()                         # (the episode's parameters: the ground randomizer's friction)
     same(vs[0].get_state(), vs[1].get_state(), "state after the reset")
     np.testing.assert_allclose(vs[0].get_state().cpu().numpy(), e.get_state(), atol=1e-5)
     rng = np.random.default_rng(3)
@@ -68,9 +75,27 @@ def test_both_step_kernels_agree_and_follow_the_emulation(torch_cuda, monkeypatc
                 v.set_rack(True)
             set_rack(e, True)
         a = stop_actions(rng, n, vs[0].action_dim, k)
+        # the oracle's step from the state the device steps from (this run is not re-seated: the device goes its own way)
+        s0 = vs[0].get_state().cpu().numpy().astype(np.float64)
+        hung = vs[0].get_info("rack").cpu().numpy()[:, 0] > 0.5
+        for p in (o, o32):
+            p.set_state(s0)
+            p.set_rack(False, ~hung); p.set_rack(True, hung)
         for v in vs:
             v.step_tensor(t.from_numpy(a).to(v.device))
         step_rack(e, a, 0)
+        o.step(a); o32.step(a)
+        s64, s32, sd = o.get_state(), o32.get_state(), vs[0].get_state().cpu().numpy().astype(np.float64)
+        # yardstick: strict (pose 5e-6, base velocity 5e-4) where the step map is smooth; tolerance + 5 x |oracle32 - oracle64| where the
+        # rack's bound binds in either oracle build, a joint is at its stop or a link touches (clamp edges)
+        r64, r32 = o.get_info(15), o32.get_info(15)
+        edge = (np.abs(r64[:, 1:7]).max(1) >= 0.999 * Y.RACK_BOUND) | (np.abs(r32[:, 1:7]).max(1) >= 0.999 * Y.RACK_BOUND) | (o.get_info(5)[:, 0] > 0)
+        edge |= ((s0[:, 13:25] <= Y.JOINT_LO) | (s0[:, 13:25] >= Y.JOINT_HI) | (s64[:, 13:25] <= Y.JOINT_LO) | (s64[:, 13:25] >= Y.JOINT_HI)).any(1)
+        spread = np.where(edge[:, None], Y.group_spread(s32, s64, base), 0.0)
+        lim = Y.bound(spread, base, 13)
+        d = np.abs(sd[:, :13] - s64[:, :13])
+        print(f"step {k}: {int(edge.sum())} edge rows; worst |device - oracle64| / bound {float((d / lim).max()):.3f}")
+        assert (d <= lim).all(), f"base state against the oracle, step {k}: (environment, column) {np.argwhere(d > lim)[:8].tolist()}, |d| / bound {float((d / lim).max())}"
         same(vs[0].get_state(), vs[1].get_state(), f"state, step {k}")
         same(vs[0].get_info("rack"), vs[1].get_info("rack"), f"rack info, step {k}")
         dev, emu = vs[0].get_state().cpu().numpy(), e.get_state()
@@ -256,3 +281,26 @@ def test_set_rack_never_waits_for_the_device(torch_cuda):
     finally:
         t.cuda.set_sync_debug_mode("default")
     assert (v.get_info("rack").cpu().numpy()[:, 0] == 1.0).all()
+
+
+def vec_device(cfg, meta):
+    import yardstick as Y
+    from qs_amd.vec_env import QuadrupedVecEnv
+    v = QuadrupedVecEnv.from_config(cfg, meta)
+    v.reset()
+    return Y.VecEnvDevice(v)
+
+
+@pytest.mark.parametrize("case", ["hung_cone", "hung_pyramid", "low_anchor", "low_anchor_sweeps3", "rehang", "stops"])
+def test_rack_against_the_oracle(torch_cuda, case):
+    """push_rack_cases.RACK_CASES on the device (n = 16, settle_steps = 300), every step from the oracle's state: state, observation,
+    reward, torques, foot forces and the rack's reaction (force 0.5 N + 2 %, torque yardstick.RACK_FIELDS) strictly where the step map is
+    smooth; tolerance + 5 x |oracle32 - oracle64| where the rack's bound binds in either oracle build or a link is on the ground; hung
+    flags equal on all three before and after every step.
+    hung_*: RL interface, random actions, 40 steps.  low_anchor: the anchor of meta["rack"] 4 mm below the standing height, so that the
+    rack's rows and the feet's share one solve (at least 100 rows hung with a foot in contact); low_anchor_sweeps3: the same with three PGS
+    sweeps, where the order of the rows -- the rack's before the contacts -- still shows in the result.  rehang: a third released at step 4, all
+    hung again at step 12 while falling (at least 20 rows with the bound binding).  stops: raw torques drive the calves into their stops
+    (at least 16 rows with a joint-limit row next to the rack's).  The CPU twins are tests/test_emu_rack.py::test_rack_against_the_oracle."""
+    import push_rack_cases as P
+    P.check(P.run(case, P.RACK_CASES, vec_device), f"test_gpu_rack[{case}]")

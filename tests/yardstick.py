@@ -99,13 +99,53 @@ class Yardstick:
         return bad
 
 
+def split_rack(extra):
+    """a device's or an oracle's `rack` rows [n, 8] (QS_INFO_RACK) as the two compared groups: the reaction's force and its torque"""
+    if "rack" in extra:
+        r = np.asarray(extra.pop("rack"), np.float64)
+        extra["rack_force"], extra["rack_torque"] = r[:, 1:4], r[:, 4:7]
+    return extra
+
+
 def oracle_extra(o):
-    """the oracle-side values of the optional fields: PD torque, foot forces, the end-of-episode bonus the task would add now"""
-    return dict(torque=o.get_info(2), foot_force=o.get_info(0), reward_end=o.eval_reward(1))
+    """the oracle-side values of the optional fields: PD torque, foot forces, the end-of-episode bonus the task would add now; with a rack,
+    its reaction"""
+    out = dict(torque=o.get_info(2), foot_force=o.get_info(0), reward_end=o.eval_reward(1))
+    if getattr(o, "on_rack", False):
+        out["rack"] = o.get_info(15)
+    return split_rack(out)
 
 
 EXTRA_FIELDS = dict(torque=(12, 5e-3), foot_force=(4, 0.5), reward_end=(1, 2e-4))
-EXTRA_RTOL = dict(foot_force=2e-2, reward_end=1e-3, reward=1e-3)
+EXTRA_RTOL = dict(foot_force=2e-2, reward_end=1e-3, reward=1e-3, rack_force=2e-2, rack_torque=2e-2)
+# The rack's reaction (handles with a rack).  Force: foot_force's floor and relative part, the project's number for a constraint force read
+# as impulse / dt.  Torque (about the pivot, N m): the floor is FACTOR x the 99th percentile of |oracle32 - oracle64| over the smooth hung
+# rows of the CPU twins (tests/test_emu_rack.py measures them again: RACK_TORQUE_OWN); the relative part is the force's.
+RACK_TORQUE_OWN = dict(p50=4.0e-5, p90=5.7e-4, p99=1.32e-3)     # N m, measured over 2229 rows of the rack schedules of push_rack_cases.py (max 3.3e-3; force: p99 0.12 N)
+RACK_FIELDS = dict(rack_force=(3, 0.5), rack_torque=(3, FACTOR * RACK_TORQUE_OWN["p99"]))
+RACK_BOUND = 500.0            # N, N m: impulse bound / dt of the rack's rows
+JOINT_LO, JOINT_HI = np.tile([-1.0471975512, -0.663225115758, -2.72271363311], 4), np.tile([1.0471975512, 2.96705972839, -0.837758040957], 4)
+
+
+def apply_events(events, parties):
+    """a schedule's events of one step to the float64 oracle, the float32 oracle and the device alike: ("push", wrench [n, 6], substeps
+    [n], frame, mask or None) and ("rack", hung, mask or None)"""
+    for ev in events:
+        for p in parties:
+            if ev[0] == "push":
+                p.set_push(*ev[1:]) if hasattr(p, "set_push") else p.set_external_wrench(ev[1], ev[2], ev[3], ev[4])
+            elif ev[0] == "rack":
+                p.set_rack(ev[1], ev[2])
+            else:
+                raise ValueError(ev[0])
+
+
+def push_left(p):
+    return np.asarray(p.push_left() if hasattr(p, "push_left") else p.get_info(14)[:, 6], np.float64)
+
+
+def hung_flags(p):
+    return np.asarray(p.hung() if hasattr(p, "hung") else p.get_info(15)[:, 0], np.float64)
 
 
 def what_if(o64, snap, states, action, ys, base, base_done, trials, rng, warm=None, extra=True):
@@ -173,10 +213,16 @@ def thrown_states(s, rows, rng):
 
 
 class EmuDevice:
-    """the host lane emulation (tests/emu) behind the device protocol of resynced_parity: the kernels' arithmetic on the CPU"""
+    """the host lane emulation (tests/emu) behind the device protocol of resynced_parity: the kernels' arithmetic on the CPU.  variant None:
+    the plain full builds of Emu.step; 0 / 1 / 2: the builds of the step kernels (0 = the full build alone, 1 / 2 = k_step's /
+    k_step_dense's common-path build with its hand-over), which take pushes and -- on a handle with a rack -- the rack"""
 
-    def __init__(self, emu):
-        self.e = emu
+    def __init__(self, emu, variant=None):
+        self.e, self.variant = emu, variant
+        self.push = None
+        if variant is not None:
+            from emu.emu import push_rows
+            self.push = push_rows(emu.n)
 
     def set_state(self, s):
         self.e.set_state(s)
@@ -185,16 +231,53 @@ class EmuDevice:
         return self.e.get_state()
 
     def step(self, a):
-        return self.e.step(a)
+        if self.variant is None:
+            return self.e.step(a)
+        return self.e.step_build(a, self.variant, push=self.push)[:4]
+
+    def _cancel(self, mask):
+        if self.push is not None:       # (the push rows live with the caller of the emulation's step: a reset cancels them here)
+            self.push[np.asarray(mask).astype(bool), 6] = 0.0
 
     def reset(self, mask):
-        self.e.reset(mask)
+        self._cancel(mask)
+        if self.variant is not None and self.e.on_rack():
+            from emu.emu import reset_rack
+            reset_rack(self.e, mask)
+        else:
+            self.e.reset(mask)
 
     def reset_to(self, mask, states):
-        self.e.reset_to(states, mask)
+        self._cancel(mask)
+        if self.variant is not None and self.e.on_rack():
+            from emu.emu import reset_to_rack
+            reset_to_rack(self.e, states, mask)
+        else:
+            self.e.reset_to(states, mask)
+
+    def set_push(self, wrench, substeps, frame, mask=None):
+        m = np.ones(self.e.n, bool) if mask is None else np.asarray(mask).astype(bool)
+        self.push[m, :6] = np.broadcast_to(np.asarray(wrench, np.float32), (self.e.n, 6))[m]
+        self.push[m, 6] = np.broadcast_to(np.asarray(substeps, np.float32), (self.e.n,))[m]
+        self.push[m, 7] = {"link": 1, "world": 2}[frame]
+
+    def push_left(self):
+        return self.push[:, 6].copy()
+
+    def set_rack(self, hung, mask=None):
+        from emu.emu import set_rack
+        set_rack(self.e, hung, mask)
+
+    def hung(self):
+        from emu.emu import rack_info
+        return rack_info(self.e)[:, 0]
 
     def extra(self):
-        return dict(torque=self.e.get("R_TAU_PD", 12), foot_force=self.e.get("R_FOOT_FORCE", 4))
+        out = dict(torque=self.e.get("R_TAU_PD", 12), foot_force=self.e.get("R_FOOT_FORCE", 4))
+        if self.variant is not None and self.e.on_rack():
+            from emu.emu import rack_info
+            out["rack"] = rack_info(self.e)
+        return out
 
     def flags(self):
         return self.e.get("R_FOOT_CONTACT", 4)
@@ -226,7 +309,28 @@ class VecEnvDevice:
         out = dict(reward_end=self.v.get_info("reward_end").cpu().numpy()[:, :1])
         if self.v.cfg.info_fields:
             out.update(torque=self.v.get_info("torque").cpu().numpy(), foot_force=self.v.get_info("foot_force").cpu().numpy())
+        if getattr(self.v, "on_rack", False):
+            out["rack"] = self.v.get_info("rack").cpu().numpy()
         return out
+
+    def set_push(self, wrench, substeps, frame, mask=None):
+        idx = None if mask is None else np.flatnonzero(np.asarray(mask)).tolist()
+        if idx is not None and not idx:
+            return
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(wrench, np.float32), (self.v.num_envs, 6)))
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(substeps, np.int32), (self.v.num_envs,)))
+        self.v.apply_external_force(w[:, :3], w[:, 3:], substeps=k, frame=frame, indices=idx)
+
+    def push_left(self):
+        return self.v.get_info("external_wrench").cpu().numpy()[:, 6]
+
+    def set_rack(self, hung, mask=None):
+        idx = None if mask is None else np.flatnonzero(np.asarray(mask)).tolist()
+        if idx is None or idx:
+            self.v.set_rack(hung, indices=idx)
+
+    def hung(self):
+        return self.v.get_info("rack").cpu().numpy()[:, 0]
 
     def flags(self):
         return self.v.get_info("foot_contact").cpu().numpy() if self.v.cfg.info_fields else None
@@ -239,20 +343,31 @@ def rough_action(d):
     return (np.tile([0.0, -1.0, 1.0], 4)[:d] if d != 4 else np.tile([-1.0, 1.0], 2)).astype(np.float32)
 
 
-def resynced_parity(o, o32, dev, cfg, layout, steps=100, thrown_steps=0, seed=1, trials=12):
+def resynced_parity(o, o32, dev, cfg, layout, steps=100, thrown_steps=0, seed=1, trials=12, schedule=None, actions=None):
     """One env.step after another from the ORACLE's state (so that chaotic divergence cannot accumulate): the device against the float64
     oracle `o`, strictly wherever no non-foot link touched the ground inside the step, and under the yardstick of this module where one did
     (the many-rows solve: an impact).  `o32` is the oracle's float32 build, stepped alongside from the same states.  After `steps` steps of
     the scripted hops `thrown_steps` more in which half of the robots start the step thrown at the floor (thrown_states): hundreds of
     impacts instead of the handful a hopping run meets.  Returns the record of what was compared how (the impact steps' |device -
-    oracle64| next to the oracle's own float32 / float64 spread)."""
+    oracle64| next to the oracle's own float32 / float64 spread).
+
+    schedule (optional): step index -> events (apply_events) -- pushes to issue, racks to release or hang -- applied to `o`, `o32` and the
+    device alike before that step; every step then asserts that the pushes' remaining-substeps column is EQUAL on all three before and
+    after it, and so are the hung flags of handles with a rack.  With a rack (o.on_rack) its reaction is compared as two more groups
+    (RACK_FIELDS), and a row in which the rack's bound binds in either oracle build (a component within 0.1 % of 500 N) is a clamp edge:
+    held by the spread rule like the impact rows, not strictly.  actions (optional): (step, the step's default actions) -> actions.  The
+    record then also counts what the schedule is there for (coverage).  Without these arguments: what the function always did."""
     n, d = cfg.n_envs, cfg.action_dim
-    ys = Yardstick(layout, EXTRA_FIELDS)
+    racked = bool(getattr(o, "on_rack", False))
+    ext = racked or schedule is not None
+    ys = Yardstick(layout, dict(EXTRA_FIELDS, **RACK_FIELDS) if racked else EXTRA_FIELDS)
     rng, prng = np.random.default_rng(seed), np.random.default_rng(seed + 1000)
     o32_ok = np.ones(n, bool)
     names = [g[0] for g in STATE_GROUPS]
     rec = dict(env_steps=0, impact_env_steps=0, second_yardstick_env_steps=0, done_on_one_side_only=0, flag_flips=0, outliers=[],
                impact_dev={k: [] for k in names}, impact_own={k: [] for k in names})
+    if ext:
+        rec.update(push_contact_env_steps=0, rack_bound_rows=0, rack_contact_rows=0, rack_limit_rows=0, rack_own_smooth=dict(rack_force=[], rack_torque=[]))
     strict = {k: np.zeros((n, len(g))) for k, (g, _) in ys.fields.items()}
     stance = o.get_state()          # (the caller has reset all three)
     for i in range(steps + thrown_steps):
@@ -262,11 +377,31 @@ def resynced_parity(o, o32, dev, cfg, layout, steps=100, thrown_steps=0, seed=1,
         s = o.get_state()
         if i >= steps:
             s = thrown_states(s, np.arange(n) % 2 == (i % 2), rng)
+        if actions is not None:
+            a = np.asarray(actions(i, a), np.float32)
         o.set_state(s); o32.set_state(s); dev.set_state(s.astype(np.float32))
+        if schedule is not None:
+            apply_events(schedule.get(i, ()), (o, o32, dev))
+        if ext:
+            left0, hung0 = push_left(o), hung_flags(o) if racked else np.zeros(n)
+            for name, p in (("float32 oracle", o32), ("device", dev)):
+                assert np.array_equal(push_left(p), left0), f"remaining substeps before step {i}, {name}: {push_left(p).tolist()} against {left0.tolist()}"
+                assert not racked or np.array_equal(hung_flags(p), hung0), f"hung flags before step {i}, {name}"
         snap = o.snapshot()
         r64, r32, rd = o.step(a), o32.step(a), dev.step(a)
-        ref, own, got = ys.collect(o, r64, oracle_extra(o)), ys.collect(o32, r32, oracle_extra(o32)), ys.collect(dev, rd, dev.extra())
+        ref, own, got = ys.collect(o, r64, oracle_extra(o)), ys.collect(o32, r32, oracle_extra(o32)), ys.collect(dev, rd, split_rack(dev.extra()))
         hit = o.get_info(5)[:, 0] > 0
+        if ext:
+            left1 = push_left(o)        # (an episode that ended on one side only is excused or refused below; its count follows its episode)
+            for name, p, ok in (("float32 oracle", o32, r32[2] == r64[2]), ("device", dev, rd[2] == r64[2])):
+                assert np.array_equal(push_left(p)[ok], left1[ok]), f"remaining substeps after step {i}, {name}: {push_left(p).tolist()} against {left1.tolist()}"
+                assert not racked or np.array_equal(hung_flags(p), hung_flags(o)), f"hung flags after step {i}, {name}"
+        binding = np.zeros(n, bool)
+        if racked:      # the rack's bound binds in either oracle build: a clamp edge, under the spread rule
+            for r in (ref, own):
+                binding |= np.maximum(np.abs(r["rack_force"]).max(axis=1), np.abs(r["rack_torque"]).max(axis=1)) >= 0.999 * RACK_BOUND
+        impact = hit
+        hit = hit | binding
         second = None
         # an episode that ends on one side only: allowed where the ORACLE's own verdict flips between its two builds or from a state 1e-6
         # away (a link that reaches its contact range in the step's last substep); such an environment is not compared in this step
@@ -277,7 +412,19 @@ def resynced_parity(o, o32, dev, cfg, layout, steps=100, thrown_steps=0, seed=1,
             assert not (odd & ~excused).any(), f"done / truncated step {i}: environments {np.flatnonzero(odd & ~excused).tolist()} (device {rd[2][odd].tolist()}, oracle {r64[2][odd].tolist()})"
             rec["done_on_one_side_only"] += int(odd.sum())
         cmp_ = ~odd
-        rec["env_steps"] += int(cmp_.sum()); rec["impact_env_steps"] += int((hit & cmp_).sum())
+        rec["env_steps"] += int(cmp_.sum()); rec["impact_env_steps"] += int((impact & cmp_).sum())
+        if ext:
+            touching = (o.get_info(1) > 0.5).any(axis=1)
+            s1 = ref["state"]
+            at_stop = ((s[:, 13:25] <= JOINT_LO) | (s[:, 13:25] >= JOINT_HI) | (s1[:, 13:25] <= JOINT_LO) | (s1[:, 13:25] >= JOINT_HI)).any(axis=1)
+            rec["push_contact_env_steps"] += int(((left0 > 0) & touching & cmp_).sum())
+            rec["rack_bound_rows"] += int((binding & cmp_).sum())
+            rec["rack_contact_rows"] += int(((hung0 > 0) & touching & cmp_).sum())
+            rec["rack_limit_rows"] += int(((hung0 > 0) & at_stop & cmp_).sum())
+            if racked:
+                smooth = ~hit & cmp_ & (hung0 > 0) & o32_ok
+                for k in ("rack_force", "rack_torque"):
+                    rec["rack_own_smooth"][k] += np.abs(own[k] - ref[k]).max(axis=1)[smooth].tolist()
         fl = dev.flags()
         same = np.ones((n, 4), bool)
         if fl is not None:
