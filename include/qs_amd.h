@@ -457,12 +457,57 @@ int qs_ac_bootstrap(qs_ac* h, const float* terminal_obs, const uint8_t* truncate
 int qs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const uint8_t* last_dones, int T, int N,
            float gamma, float lambda, float* advantages, float* returns, void* hip_stream);
 
+/* ---- Device snapshots: save, restore and fork environments (what pybullet.saveState / restoreState are to the reference's simulator; the CPU
+ * oracle's qso_snapshot / qso_restore).  A snapshot is one row of qs_snapshot_info::row_floats floats per environment, in DEVICE memory owned by
+ * the caller (16-byte aligned): [the environment's whole record | its push row | its last observation | its terminal observation], layout in
+ * csrc/qs_snapshot.h.  That is everything a step reads: the rigid-body state, the action filter's history and the last action, the task block,
+ * the wrapper's phase machine, the CPG's oscillators, the demo counter, the episode / step / noise counters, the randomised parameters, the
+ * payload block or the rack's hung flag, the pending push.  Randomizer draws are keyed by (seed, global environment id, episode), observation
+ * noise by (seed, environment id, total steps), and both counters are in the record: a restored handle continues bit for bit as the run that
+ * was never interrupted, noise, randomizers, auto-resets and look-ahead included.
+ * Not part of a snapshot and left untouched by qs_restore and qs_fork: the telemetry counters (qs_counter, qs_stats), the trace tap, the
+ * demonstration table, the stream, the timing state and the host path's result blocks.  The handle's configuration and rack are not part of
+ * it either: the digests below say whether a row fits a handle.
+ * All three calls are stream-ordered and never wait for the device. */
+struct qs_snapshot_info {
+    uint64_t bytes;              /* n_envs * row_floats * 4: the size of the rows */
+    int32_t n_envs, row_floats, rec_floats, push_floats, obs_dim;
+    int32_t layout_version;      /* bumped by whoever changes csrc/qs_layout.h or the row (csrc/qs_snapshot.h) */
+    uint64_t layout_digest;      /* FNV-1a over what gives a row its meaning: layout_version, the record's stride, obs_dim, action_dim, n_envs, task,
+                                  * wrapper mode, action-space mode, payload_soft, rack on.  Rows restore only into a handle with the same one. */
+    uint64_t config_digest;      /* FNV-1a over every byte of the handle's qs_config and qs_rack: equal = the same simulation (an exact resume);
+                                  * rows with the same layout_digest and another config_digest (another seed, other gains) restore as well and
+                                  * continue under the handle's own configuration */
+};
+/* (a struct tag, not a typedef: the entry below carries the same name) */
+int qs_snapshot_info(const qs_handle* h, struct qs_snapshot_info* out);
+/* handle -> rows.  mask: device [N] bytes or NULL = all; rows: device [N, row_floats].  The rows of unmasked environments are not written. */
+int qs_snapshot(qs_handle* h, const uint8_t* mask, float* rows);
+/* rows -> handle: record, push row, last observation (qs_get_obs answers with it) and terminal observation of the masked environments.  The
+ * look-ahead window of a restored environment is re-seated on the restored episode X: the states of X + 1 .. X + K are queued again; a slot
+ * that holds another episode is not taken (its tag says so) and that reset settles in place, counted as a stall, with the same bits.  A push may
+ * be pending in the rows, so the step launches read the push rows again (one float per environment) until a reset of all environments.  The
+ * caller checks the digests (qs_amd/snapshot.py does): the library cannot know where the rows came from. */
+int qs_restore(qs_handle* h, const uint8_t* mask, const float* rows);
+/* Environment to environment inside the handle.  src_of: device [N] int32, the source of each environment; -1 or its own index = leave alone.
+ * For every i with a source s != i in range, record, push row and both observations of i become those of s, EXCEPT the record's episode
+ * number and total-step counter, which stay i's own: the fork keeps its identity -- its future randomizer draws, its noise stream and its
+ * look-ahead window -- so no look-ahead slot is invalidated and the window is not touched.  The call behaves as if every source were read
+ * before any destination is written (chains i <- j <- k and swaps are legal): a gather launch into staging rows owned by the handle
+ * (allocated at the first fork), then a scatter launch.  A source outside [-1, N) leaves that environment alone, and the next qs_stats or
+ * qs_counter fails once, naming the first such environment (as for qs_set_external_wrench). */
+int qs_fork(qs_handle* h, const int32_t* src_of);
+/* VecNormalize.returns, the per-environment discounted returns a qs_norm carries between steps: device [N] float64, stream-ordered copies.
+ * With qs_norm_get_stats / qs_norm_set_stats they are all of a normalisation handle's state. */
+int qs_norm_get_returns(qs_norm* h, double* returns /* device [N] */);
+int qs_norm_set_returns(qs_norm* h, const double* returns /* device [N] */);
+
 const char* qs_last_error(void);
 const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 9
 int qs_abi_version(void);
 

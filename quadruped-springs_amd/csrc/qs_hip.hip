@@ -176,7 +176,8 @@ enum { CTL_SETTLE_SUBSTEPS = 0, CTL_RESETS = 1, CTL_SERVED = 2, CTL_SETTLED = 3,
        /* (CTL_DEV + 2 .. + 11: the counting builds' counters, qs_core.h, tools/probe_*.py) */
        CTL_PUSH_REFUSED = 22 + QS_COHORTS /* 1 + the first environment whose row qs_set_external_wrench refused, 0 if none */,
        CTL_RENDER_REFUSED = 23 + QS_COHORTS /* 1 + the first position of a qs_render call's env_ids that held an id out of range, 0 if none */,
-       CTL_N = 24 + QS_COHORTS };
+       CTL_FORK_REFUSED = 24 + QS_COHORTS /* 1 + the first environment whose source qs_fork refused (outside [-1, N)), 0 if none */,
+       CTL_N = 25 + QS_COHORTS };
 
 // settled-state fields a look-ahead reset copies into the record (everything the 2500-substep settle determines), and the slot's tag.
 // Every load is issued before the first value is used: as four rolled loops (`rec[i] = src[i]`) the copy was a load, a wait and an LDS write
@@ -700,6 +701,7 @@ struct qs_handle {
     float* trace_rows; int trace_env;
     float* d_demo; int demo_len;   // qs_set_demo
     float* d_push;          // [N][QS_PUSH_F]: qs_set_external_wrench
+    float* d_fork;          // qs_fork's staging rows (qs_snapshot.hip; allocated at the first fork)
     qs_rack rack;           // qs_create_ex: on = 1 -> the rack's kernels (k_step_rack, k_reset_rack, k_lookahead_fill_rack)
     int push_live;          // a push may be pending: the step launches read d_push (cleared by a reset of every environment)
     int n_simd, step_variant;   // SIMDs of the device; 0 = pick k_step / k_step_dense by grid size, 1 / 2 = forced (QS_STEP_VARIANT)
@@ -877,6 +879,7 @@ void qs_destroy(qs_handle* h) {   // also used on a partially built handle (null
     if (h->d_stage_jobs) hipFree(h->d_stage_jobs);
     if (h->d_demo) hipFree(h->d_demo);
     if (h->d_push) hipFree(h->d_push);
+    if (h->d_fork) hipFree(h->d_fork);
     host_path_free(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -1273,9 +1276,15 @@ int qs_set_rack(qs_handle* h, const uint8_t* mask, int hung) {
     return 0;
 }
 
-// after a synchronisation: fails once if qs_set_external_wrench refused a row, or qs_render met an environment id out of range, since the last report
+// after a synchronisation: fails once if qs_set_external_wrench refused a row, qs_render met an environment id out of range or qs_fork a source
+// out of range, since the last report
 static int push_refusal(qs_handle* h) {
-    unsigned long long v = 0, r = 0;
+    unsigned long long v = 0, r = 0, f = 0;
+    QS_HIP(hipMemcpy(&f, &h->d_stats[CTL_FORK_REFUSED], sizeof(f), hipMemcpyDeviceToHost));
+    if (f != 0) {   // (goes first; the others then wait for the next report)
+        QS_HIP(hipMemset(&h->d_stats[CTL_FORK_REFUSED], 0, sizeof(f)));
+        QS_FAIL(-1, "qs_fork refused the source of environment %llu (and maybe others): outside [-1, %d); those environments were left alone", f - 1, h->cfg.n_envs);
+    }
     QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_PUSH_REFUSED], sizeof(v), hipMemcpyDeviceToHost));
     QS_HIP(hipMemcpy(&r, &h->d_stats[CTL_RENDER_REFUSED], sizeof(r), hipMemcpyDeviceToHost));
     if (v == 0 && r != 0) {   // (a push refusal goes first; this one then waits for the next report)
@@ -1293,6 +1302,15 @@ static int push_refusal(qs_handle* h) {
 int qs_render_view(qs_handle* h, QsRenderView* v) {
     v->rec = h->d_rec; v->n_envs = h->cfg.n_envs; v->payload_soft = h->cfg.payload_soft; v->device = h->device;
     v->stream = h->stream; v->refused = h->d_stats + CTL_RENDER_REFUSED;
+    return 0;
+}
+static_assert(QS_PUSH_F == 8, "qs_snapshot.h's PUSH_F");
+int qs_snapshot_view(qs_handle* h, QsSnapshotView* v) {
+    v->cfg = &h->cfg; v->rack = &h->rack;
+    v->rec = h->d_rec; v->push = h->d_push; v->obs = h->d_obs; v->term = h->d_term_obs;
+    v->la_cur = h->la.cur; v->la_handed = h->la.handed; v->la_K = h->la.K;
+    v->device = h->device; v->stream = h->stream;
+    v->fork_refused = h->d_stats + CTL_FORK_REFUSED; v->fork_rows = &h->d_fork; v->push_live = &h->push_live;
     return 0;
 }
 extern "C" {

@@ -21,3 +21,18 @@ struct QsRenderView {
     unsigned long long* refused;   // device counter: 1 + the first position of env_ids that held an id out of range, 0 if none
 };
 int qs_render_view(qs_handle* h, QsRenderView* v);
+
+// What the snapshot entries (qs_snapshot.hip) read and write of a simulation handle.
+struct qs_config;
+struct qs_rack;
+struct QsSnapshotView {
+    const qs_config* cfg; const qs_rack* rack;
+    float* rec; float* push; float* obs; float* term;   // records [N][QS_REC], push rows [N][QS_PUSH_F], last and terminal observations [N][obs_dim]
+    int* la_cur; int* la_handed; int la_K;              // the look-ahead window (null / 0 without one)
+    int device;
+    hipStream_t stream;
+    unsigned long long* fork_refused;   // device counter: 1 + the first environment whose source qs_fork refused, 0 if none
+    float** fork_rows;                  // the handle's staging rows of qs_fork [N][row_floats] (allocated at the first fork, freed by qs_destroy)
+    int* push_live;                     // qs_restore sets it: a push may be pending in the restored rows
+};
+int qs_snapshot_view(qs_handle* h, QsSnapshotView* v);

@@ -298,6 +298,20 @@ static int norm_launch(qs_norm* h, const qs_norm_io& io, int training, int with_
     return 0;
 }
 
+// VecNormalize.returns, stream-ordered (what a snapshot of the wrapper carries next to the statistics)
+int qs_norm_get_returns(qs_norm* h, double* returns) {
+    if (!h || !returns) QN_FAIL(-1, "null argument");
+    QS_ON_DEVICE(h);
+    QN_HIP(hipMemcpyAsync(returns, h->d_ret, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+int qs_norm_set_returns(qs_norm* h, const double* returns) {
+    if (!h || !returns) QN_FAIL(-1, "null argument");
+    QS_ON_DEVICE(h);
+    QN_HIP(hipMemcpyAsync(h->d_ret, returns, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
 int qs_norm_dims(const qs_norm* h, int* n_envs, int* obs_dim, int* device) {
     if (!h) QN_FAIL(-1, "null handle");
     if (n_envs) *n_envs = h->n;

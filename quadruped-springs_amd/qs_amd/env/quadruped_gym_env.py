@@ -379,6 +379,21 @@ class QuadrupedGymEnv(GymEnv):
         self._last_action = np.asarray(self._settling_action, float)
         return self._as_dict(flat)
 
+    def snapshot(self):
+        """The one robot as an EnvSnapshot (QuadrupedVecEnv.snapshot; what pybullet.saveState is to the reference), with this view's own
+        _last_action in extras["gym_env"]."""
+        snap = self._vec.snapshot()
+        snap.extras["gym_env"] = dict(last_action=np.asarray(self._last_action, np.float64).copy())
+        return snap
+
+    def restore(self, snap):
+        """Back to `snap`; returns the observation dict as reset() does."""
+        flat = self._vec.restore(snap)[0].cpu().numpy()
+        x = snap.extras.get("gym_env")
+        if x is not None:
+            self._last_action = np.asarray(x["last_action"], np.float64).copy()
+        return self._as_dict(flat)
+
     def get_reward_end_episode(self):
         """gym_env.py:363-365: the task's end-of-episode bonus / malus for the current state."""
         return float(self._vec.get_info("reward_end")[0, 0])

@@ -20,6 +20,7 @@ EXPORTS = (
     "qs_norm_step_io", "qs_host_set_norm",
     "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
     "qs_ac_create", "qs_ac_destroy", "qs_ac_set_stream", "qs_ac_set_params", "qs_ac_collect", "qs_ac_values", "qs_ac_bootstrap", "qs_gae",
+    "qs_snapshot_info", "qs_snapshot", "qs_restore", "qs_fork", "qs_norm_get_returns", "qs_norm_set_returns",
 )
 
 
@@ -136,6 +137,14 @@ def load():
         lib.qs_ac_values.argtypes = [vp, vp, vp, vp]
         lib.qs_ac_bootstrap.argtypes = [vp, vp, vp, f32, vp]
         lib.qs_gae.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp]
+    if hasattr(lib, "qs_snapshot_info"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
+        from .snapshot import SnapshotInfo
+        lib.qs_snapshot_info.argtypes = [vp, C.POINTER(SnapshotInfo)]
+        lib.qs_snapshot.argtypes = [vp, vp, vp]
+        lib.qs_restore.argtypes = [vp, vp, vp]
+        lib.qs_fork.argtypes = [vp, vp]
+        lib.qs_norm_get_returns.argtypes = [vp, vp]
+        lib.qs_norm_set_returns.argtypes = [vp, vp]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)

@@ -46,6 +46,30 @@ class ReferenceStateInitVecEnv:
         v.set_demo_counter(self.random_el.astype(np.int32), mask=mask.astype(np.uint8))
         return obs
 
+    # ---- snapshots (QuadrupedVecEnv.snapshot / restore; fork is the wrapped environment's: this wrapper keeps nothing per fork but the
+    # bookkeeping below, which a fork leaves its own)
+    def snapshot(self, indices=None, out=None):
+        """the wrapped environment's snapshot with this wrapper's state in extras["rsi"]: the generator's state and the reset counters"""
+        import json
+        snap = self.venv.snapshot(indices, out)
+        snap.extras["rsi"] = dict(rng=json.dumps(self._rng.bit_generator.state), counter=self._counter.copy(), random_el=self.random_el.copy())
+        return snap
+
+    def restore(self, snap, indices=None, strict=True):
+        import json
+        x = snap.extras.get("rsi")
+        if x is None:
+            raise ValueError("the snapshot carries no rsi state: it was taken below this wrapper (restore it there: env.venv.restore)")
+        obs = self.venv.restore(snap, indices, strict)
+        self._rng.bit_generator.state = json.loads(x["rng"])     # (one generator serves all environments: it goes back whole)
+        idx = slice(None) if indices is None else np.asarray(self.venv._indices(indices), np.int64)
+        self._counter[idx] = np.asarray(x["counter"])[idx]
+        self.random_el[idx] = np.asarray(x["random_el"])[idx]
+        return obs
+
+    def fork(self, src=None, dst=None, src_of=None):
+        return self.venv.fork(src, dst, src_of)
+
     def reset_tensor(self):
         if not self.enable_wrapper:
             return self.venv.reset_tensor()

@@ -84,3 +84,14 @@ class ShardedVecEnv:
             rows[:, self.obs_dim + 1] = done.to(torch.float32) + 2 * trunc.to(torch.float32)
         self._all_gather(g)
         return self._unpack(g) if unpack else g
+
+    # ---- snapshots and forks: this rank's shard only, no collective (indices are the LOCAL environment's)
+    def snapshot(self, indices=None, out=None):
+        return self.env.snapshot(indices, out)
+
+    def restore(self, snap, indices=None, strict=True):
+        """-> this rank's observation rows (the next step() gathers as usual)"""
+        return self.env.restore(snap, indices, strict)
+
+    def fork(self, src=None, dst=None, src_of=None):
+        return self.env.fork(src, dst, src_of)

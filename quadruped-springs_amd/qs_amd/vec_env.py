@@ -284,6 +284,150 @@ class QuadrupedVecEnv(SB3VecEnv):
         # allocator before the kernel has read them, the staging blocks are held by the host allocator until their copies are done)
         self._push_keep = (w, k, m, keep)
 
+    # ---- snapshots and forks (include/qs_amd.h qs_snapshot / qs_restore / qs_fork)
+    def snapshot_info(self):
+        """the qs_snapshot_info fields of this handle as a dict: the row's size, and the digests that say which snapshots fit it"""
+        from .snapshot import SnapshotInfo
+        info = SnapshotInfo()
+        _lib.check(self.lib.qs_snapshot_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def _mask_of(self, indices):
+        """device uint8 [N] with ones at `indices` (None: no mask = all); host indices are checked here and go over without blocking"""
+        if indices is None:
+            return None
+        t = self.torch
+        if isinstance(indices, t.Tensor) and indices.device == self.device:
+            if indices.dtype == t.bool or indices.dtype == t.uint8:
+                if tuple(indices.shape) != (self.num_envs,):
+                    raise ValueError(f"a mask must have shape {(self.num_envs,)}, got {tuple(indices.shape)}")
+                return indices.to(t.uint8).contiguous()
+            return t.zeros(self.num_envs, dtype=t.uint8, device=self.device).index_fill_(0, indices.to(t.int64), 1)
+        idx = np.asarray(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices), np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.num_envs):
+            raise ValueError(f"environment ids must lie in [0, {self.num_envs}), got {idx.min()} .. {idx.max()}")
+        m = np.zeros(self.num_envs, np.uint8)
+        m[idx] = 1
+        return t.from_numpy(m).pin_memory().to(self.device, non_blocking=True)
+
+    def snapshot(self, indices=None, out=None):
+        """The environments `indices` (None = all) as an EnvSnapshot: one row per environment with everything a step reads (the record, the
+        pending push, the last and the terminal observation).  One launch on the current stream; nothing is waited for.  out: an earlier
+        snapshot of this handle whose tensor is written again -- only the rows of `indices` change -- so a control loop allocates nothing."""
+        from .snapshot import EnvSnapshot, check_fits
+        t = self.torch
+        info = self.snapshot_info()
+        if out is None:
+            rows = t.zeros((info["n_envs"], info["row_floats"]), dtype=t.float32, device=self.device)
+            snap = EnvSnapshot(rows, info)
+        else:
+            check_fits(out.info, info, strict=True)
+            rows = out.rows
+            if rows.device != self.device or rows.dtype != t.float32 or not rows.is_contiguous() or tuple(rows.shape) != (info["n_envs"], info["row_floats"]):
+                raise ValueError(f"out.rows must be a contiguous float32 tensor of shape {(info['n_envs'], info['row_floats'])} on {self.device}")
+            snap = out
+        m = self._mask_of(indices)
+        self._stream()
+        _lib.check(self.lib.qs_snapshot(self.h, None if m is None else self._ptr(m), self._ptr(rows)))
+        self._snap_keep = m
+        return snap
+
+    def restore(self, snap, indices=None, strict=True):
+        """The environments `indices` (None = all) go back to `snap`; returns the observation tensor, as reset_tensor does.  strict=True
+        demands a snapshot of the same configuration (equal config_digest): from there the handle continues bit for bit as the run the
+        snapshot was taken from.  strict=False takes any snapshot of the same layout (equal layout_digest), e.g. of another seed: the robots
+        continue under THIS handle's configuration.  Anything else raises ValueError naming the first differing field.  The `infos` entries
+        of the restored environments are cleared (dicts handed out earlier are not changed under copy_outputs=True)."""
+        from .snapshot import check_fits
+        t = self.torch
+        check_fits(snap.info, self.snapshot_info(), strict=strict)
+        rows = snap.rows
+        if tuple(rows.shape) != (snap.info["n_envs"], snap.info["row_floats"]) or rows.dtype != t.float32:
+            raise ValueError(f"snapshot rows must be float32 of shape {(snap.info['n_envs'], snap.info['row_floats'])}, got {rows.dtype} {tuple(rows.shape)}")
+        if rows.device != self.device or not rows.is_contiguous():
+            rows = rows.contiguous().to(self.device)
+        m = self._mask_of(indices)
+        self._stream()
+        _lib.check(self.lib.qs_restore(self.h, None if m is None else self._ptr(m), self._ptr(rows)))
+        _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
+        self._snap_keep = (m, rows)
+        if not self._dirty:
+            pass                                   # (every filled entry is listed there: a device-only loop never looks at its indices on the host)
+        elif indices is None:
+            self._forget_infos(None)
+        elif isinstance(indices, t.Tensor) and indices.dtype in (t.bool, t.uint8):
+            self._forget_infos(t.nonzero(indices).flatten().tolist())
+        else:
+            self._forget_infos(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices))
+        return self._obs
+
+    def _forget_infos(self, idx):
+        """the infos entries of environments `idx` (None = all) say nothing any more"""
+        idx = range(self.num_envs) if idx is None else idx
+        for i in idx:
+            if self._infos[i]:
+                if self.copy_outputs:
+                    self._infos[i] = {}
+                else:
+                    self._infos[i].clear()
+        gone = set(idx)
+        self._dirty = [i for i in self._dirty if i not in gone]
+
+    def fork(self, src=None, dst=None, src_of=None):
+        """Copy environments inside the handle, in one call (a gather launch and a scatter launch, every source read before any destination is
+        written: chains and swaps are legal).  src: one index or [M]; dst: the indices that receive them -- one source broadcasts, M sources
+        need M destinations; dst=None with one source means every other environment.  Or src_of: an int32 [N] tensor on the device, the
+        source of every environment (-1 or its own index: left alone), which goes straight to the kernel.  A fork takes its source's whole
+        record, push and observations but keeps its own episode number and total-step counter: its future randomizer draws, its noise
+        stream and its look-ahead window stay its own.  Host indices are checked here and raise; a device src_of outside [-1, N) leaves
+        that environment alone and makes the next stats() / counter() raise, naming it.  Returns the device int32 [N] sources used."""
+        t = self.torch
+        n = self.num_envs
+        if src_of is not None:
+            if src is not None or dst is not None:
+                raise ValueError("give either src (and dst) or src_of")
+            if not (isinstance(src_of, t.Tensor) and src_of.device == self.device):
+                a = np.asarray(src_of)
+                if a.dtype.kind not in "iu" or a.shape != (n,):
+                    raise ValueError(f"src_of must be {n} integers, got {a.dtype} {a.shape}")
+                if a.min() < -1 or a.max() >= n:
+                    raise ValueError(f"sources must lie in [-1, {n}), got {a.min()} .. {a.max()}")
+                so = t.from_numpy(a.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+            else:
+                if src_of.dtype.is_floating_point or src_of.dtype == t.bool or tuple(src_of.shape) != (n,):
+                    raise ValueError(f"src_of must be an integer tensor of shape {(n,)}, got {src_of.dtype} {tuple(src_of.shape)}")
+                so = src_of.to(t.int32).contiguous()
+        else:
+            if src is None:
+                raise ValueError("fork needs src or src_of")
+            s = np.atleast_1d(np.asarray(src.tolist() if isinstance(src, t.Tensor) else src))
+            if s.dtype.kind not in "iu" or s.ndim != 1 or s.size == 0:
+                raise ValueError(f"src must be an index or a list of indices, got {src!r}")
+            if dst is None:
+                if s.size != 1:
+                    raise ValueError("dst=None needs exactly one source (it then goes to every other environment)")
+                d = np.array([i for i in range(n) if i != int(s[0])], np.int64)
+            else:
+                d = np.atleast_1d(np.asarray(dst.tolist() if isinstance(dst, t.Tensor) else dst))
+                if d.size and (d.dtype.kind not in "iu" or d.ndim != 1):
+                    raise ValueError(f"dst must be a list of indices, got {dst!r}")
+                d = d.astype(np.int64)
+            if s.size != 1 and s.size != d.size:
+                raise ValueError(f"{s.size} sources for {d.size} destinations: give one source, or one per destination")
+            for name, a in (("src", s), ("dst", d)):
+                if a.size and (a.min() < 0 or a.max() >= n):
+                    raise ValueError(f"{name} must lie in [0, {n}), got {a.min()} .. {a.max()}")
+            if np.unique(d).size != d.size:
+                raise ValueError("dst names an environment twice")
+            a = np.full(n, -1, np.int32)
+            a[d] = s.astype(np.int32) if s.size > 1 else np.int32(s[0])
+            so = t.from_numpy(a).pin_memory().to(self.device, non_blocking=True)
+        self._stream()
+        _lib.check(self.lib.qs_fork(self.h, self._ptr(so)))
+        _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
+        self._fork_keep = so
+        return so
+
     def stats(self):
         a, b = C.c_uint64(), C.c_uint64()
         _lib.check(self.lib.qs_stats(self.h, C.byref(a), C.byref(b)))

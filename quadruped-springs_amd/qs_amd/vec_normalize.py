@@ -159,6 +159,67 @@ class DeviceVecNormalize:
         _lib.check(self.lib.qs_norm_set_stats(self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), float(obs_count), float(ret_mean),
                                               float(ret_var), float(ret_count)))
 
+    # ---- snapshots and forks (QuadrupedVecEnv.snapshot / restore / fork)
+    def _returns(self):
+        r = self.torch.empty(self.num_envs, dtype=self.torch.float64, device=self.device)
+        self._stream()
+        _lib.check(self.lib.qs_norm_get_returns(self.h, self._p(r)))
+        return r
+
+    def _set_returns(self, r):
+        r = self.torch.as_tensor(r, dtype=self.torch.float64).to(self.device).contiguous()
+        if tuple(r.shape) != (self.num_envs,):
+            raise ValueError(f"returns must have shape {(self.num_envs,)}, got {tuple(r.shape)}")
+        self._stream()
+        _lib.check(self.lib.qs_norm_set_returns(self.h, self._p(r)))
+        self._returns_keep = r
+
+    def snapshot(self, indices=None, out=None):
+        """The wrapped environment's snapshot with this wrapper's state in extras["vec_normalize"]: the float64 statistics, the
+        per-environment discounted returns, old_obs / old_reward.  The statistics belong to all environments: they are saved and restored
+        whole whatever `indices` says.  Reading the statistics waits for the stream (qs_norm_get_stats)."""
+        snap = self.venv.snapshot(indices, out)
+        snap.extras["vec_normalize"] = dict(stats={k: np.asarray(v, np.float64) for k, v in self.get_stats().items()}, returns=self._returns(),
+                                            old_obs=self.old_obs.clone(), old_reward=self.old_reward.clone())
+        return snap
+
+    def restore(self, snap, indices=None, strict=True):
+        """-> the observation as the step before the snapshot returned it (normalised with the restored statistics)"""
+        t = self.torch
+        x = snap.extras.get("vec_normalize")
+        if x is None:
+            raise ValueError("the snapshot carries no vec_normalize state: it was taken below this wrapper (restore it there: env.venv.restore)")
+        obs = self.venv.restore(snap, indices, strict)
+        st = {k: np.asarray(v, np.float64) for k, v in x["stats"].items()}
+        self._stream()
+        self.set_stats(st["obs_mean"], st["obs_var"], float(st["obs_count"]), float(st["ret_mean"]), float(st["ret_var"]), float(st["ret_count"]))
+        ret = t.as_tensor(x["returns"], dtype=t.float64).to(self.device)
+        old_obs = t.as_tensor(x["old_obs"], dtype=t.float32).to(self.device)
+        old_rew = t.as_tensor(x["old_reward"], dtype=t.float32).to(self.device)
+        if indices is None:
+            self._set_returns(ret)
+            self.old_obs.copy_(old_obs); self.old_reward.copy_(old_rew)
+        else:
+            m = self.venv._mask_of(indices).bool()
+            self._set_returns(t.where(m, ret, self._returns()))
+            self.old_obs.copy_(t.where(m[:, None], old_obs, self.old_obs)); self.old_reward.copy_(t.where(m, old_rew, self.old_reward))
+        if self.norm_obs:   # the handle keeps raw observations: normalise the returned buffer as a step does, without touching the statistics
+            s = self.get_stats()
+            mean = t.as_tensor(s["obs_mean"], dtype=t.float64, device=self.device)
+            inv = 1.0 / t.sqrt(t.as_tensor(s["obs_var"], dtype=t.float64, device=self.device) + self.epsilon)
+            obs.copy_(((obs.double() - mean) * inv).clamp(-self.clip_obs, self.clip_obs).float())
+        return obs
+
+    def fork(self, src=None, dst=None, src_of=None):
+        """QuadrupedVecEnv.fork; the forked environments take their sources' discounted returns and old_obs / old_reward as well"""
+        t = self.torch
+        so = self.venv.fork(src, dst, src_of).to(t.int64)
+        me = t.arange(self.num_envs, device=self.device)
+        take = t.where((so >= 0) & (so < self.num_envs), so, me)
+        self._set_returns(self._returns()[take])
+        self.old_obs.copy_(self.old_obs[take]); self.old_reward.copy_(self.old_reward[take])
+        return so
+
     def save(self, path):
         np.savez(path, clip_obs=self.clip_obs, clip_reward=self.clip_reward, gamma=self.gamma, epsilon=self.epsilon, norm_obs=self.norm_obs,
                  norm_reward=self.norm_reward, **self.get_stats())
