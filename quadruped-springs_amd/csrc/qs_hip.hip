@@ -678,10 +678,15 @@ template __global__ void k_step_dense<true, false>(QS_STEP_ARGS);
 #endif
 #else
 // ------------------------------------------------------------------ host side of the C ABI
-thread_local char qs_g_err[512] = "";   // shared with qs_norm.hip
-#define g_err qs_g_err
-#define QS_FAIL(code, ...) do { snprintf(g_err, sizeof(g_err), __VA_ARGS__); return (code); } while (0)
-#define QS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QS_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+thread_local char qs_g_err[512] = "";   // (declared in qs_host.h)
+int qs_check_device(int device) {
+    int ndev = 0;
+    hipError_t derr = hipGetDeviceCount(&ndev);
+    if (derr != hipSuccess || ndev <= 0)
+        QS_FAIL(-3, "no HIP device available (hipGetDeviceCount: %s, %d devices): this library has no CPU path", hipGetErrorString(derr), ndev);
+    if (device < 0 || device >= ndev) QS_FAIL(-3, "HIP device %d out of range (%d visible)", device, ndev);
+    return 0;
+}
 
 struct HostPath;
 struct qs_handle {
@@ -729,7 +734,7 @@ static qs::Build handle_build(const qs_handle* h) { return qs::Build::of(h->cfg,
 
 extern "C" {
 
-const char* qs_last_error(void) { return g_err; }
+const char* qs_last_error(void) { return qs_g_err; }
 // build.py passes the fingerprint of the source tree the library is compiled from (every file under csrc/, the public header, the build
 // script with its flags): a binary says itself which sources it is, and the parity gate (tools/gate.sh) records what it validated
 #ifndef QS_SOURCE_SHA
@@ -784,11 +789,7 @@ int qs_create_ex(const qs_config* cfg, const qs_rack* rack_in, int device, qs_ha
     int od = 0;
     for (int i = 0; i < cfg->n_sensors; i++) od += sensor_dim(cfg->sensors[i]);
     if (od != cfg->obs_dim) QS_FAIL(-1, "obs_dim %d does not match the sensor bundle (%d)", cfg->obs_dim, od);
-    int ndev = 0;
-    hipError_t derr = hipGetDeviceCount(&ndev);
-    if (derr != hipSuccess || ndev <= 0)
-        QS_FAIL(-3, "no HIP device available (hipGetDeviceCount: %s, %d devices): this library has no CPU path", hipGetErrorString(derr), ndev);
-    if (device < 0 || device >= ndev) QS_FAIL(-3, "HIP device %d out of range (%d visible)", device, ndev);
+    if (int rc = qs_check_device(device)) return rc;
     DeviceGuard guard(device);
     qs_handle* h = new (std::nothrow) qs_handle();
     if (!h) QS_FAIL(-4, "out of host memory");

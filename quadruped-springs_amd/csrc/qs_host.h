@@ -1,6 +1,14 @@
-// Host-side helpers shared by the C-ABI translation units (qs_hip.hip, qs_norm.hip, qs_render.hip).
+// Host-side helpers shared by the C-ABI translation units (qs_hip.hip, qs_norm.hip, qs_render.hip, qs_policy.hip, qs_ppo.hip, qs_snapshot.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdio>
+
+// The error path of every entry point: the reason goes into the calling thread's text (qs_last_error; defined in qs_hip.hip), the code is returned.
+extern thread_local char qs_g_err[512];
+#define QS_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
+#define QS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QS_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+// 0 if `device` is a visible HIP device, or -3 with the reason in qs_g_err (there is no CPU path); every *_create asks it first (qs_hip.hip)
+int qs_check_device(int device);
 
 // Entry points run on the handle's device whatever the calling thread's current device is, and leave that as they found it.
 struct DeviceGuard {

@@ -15,10 +15,6 @@
 #include "qs_amd.h"
 #include "qs_host.h"
 
-extern thread_local char qs_g_err[512];
-#define QN_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
-#define QN_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QN_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-
 struct qs_norm {
     int n, o, device;
     double clip_obs, clip_rew, gamma, eps;      // (double like SB3's Python floats: gamma = 0.99 as a float32 moved the returns' statistics by 7e-9)
@@ -215,14 +211,11 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
 extern "C" {
 
 int qs_norm_create(int n_envs, int obs_dim, double clip_obs, double clip_reward, double gamma, double epsilon, int device, qs_norm** out) {
-    if (!out || n_envs <= 0 || obs_dim <= 0 || obs_dim > 255) QN_FAIL(-1, "bad argument (n_envs %d, obs_dim %d)", n_envs, obs_dim);
-    int ndev = 0;
-    hipError_t derr = hipGetDeviceCount(&ndev);
-    if (derr != hipSuccess || ndev <= 0) QN_FAIL(-3, "no HIP device available: this library has no CPU path");
-    if (device < 0 || device >= ndev) QN_FAIL(-3, "HIP device %d out of range (%d visible)", device, ndev);
+    if (!out || n_envs <= 0 || obs_dim <= 0 || obs_dim > 255) QS_FAIL(-1, "bad argument (n_envs %d, obs_dim %d)", n_envs, obs_dim);
+    if (int rc = qs_check_device(device)) return rc;
     DeviceGuard guard(device);
     qs_norm* h = new (std::nothrow) qs_norm();
-    if (!h) QN_FAIL(-4, "out of host memory");
+    if (!h) QS_FAIL(-4, "out of host memory");
     memset(h, 0, sizeof(*h));
     h->n = n_envs; h->o = obs_dim; h->device = device; h->clip_obs = clip_obs; h->clip_rew = clip_reward; h->gamma = gamma; h->eps = epsilon;
     const int C = obs_dim + 1, S = 5 * C + 2;
@@ -253,30 +246,30 @@ void qs_norm_destroy(qs_norm* h) {
     delete h;
 }
 
-int qs_norm_set_stream(qs_norm* h, void* s) { if (!h) QN_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_norm_set_stream(qs_norm* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
 
 int qs_norm_set_stats(qs_norm* h, const double* obs_mean, const double* obs_var, double obs_count, double ret_mean, double ret_var, double ret_count) {
-    if (!h || !obs_mean || !obs_var) QN_FAIL(-1, "null argument");
+    if (!h || !obs_mean || !obs_var) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
     const int C = h->o + 1;
     double buf[2 * 256 + 2];
     for (int c = 0; c < h->o; c++) { buf[c] = obs_mean[c]; buf[C + c] = obs_var[c]; }
     buf[h->o] = ret_mean; buf[C + h->o] = ret_var; buf[2 * C] = obs_count; buf[2 * C + 1] = ret_count;
-    QN_HIP(hipStreamSynchronize(h->stream));
-    QN_HIP(hipMemcpy(QN_STAT(h, h->cur), buf, (size_t)(2 * C + 2) * sizeof(double), hipMemcpyHostToDevice));
+    QS_HIP(hipStreamSynchronize(h->stream));
+    QS_HIP(hipMemcpy(QN_STAT(h, h->cur), buf, (size_t)(2 * C + 2) * sizeof(double), hipMemcpyHostToDevice));
     double inv[256];
     for (int c = 0; c < C; c++) inv[c] = 1.0 / sqrt(buf[C + c] + (double)h->eps);
-    QN_HIP(hipMemcpy(QN_STAT(h, h->cur) + 4 * C + 2, inv, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    QS_HIP(hipMemcpy(QN_STAT(h, h->cur) + 4 * C + 2, inv, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
     return 0;
 }
 
 int qs_norm_get_stats(qs_norm* h, double* obs_mean, double* obs_var, double* obs_count, double* ret_mean, double* ret_var, double* ret_count) {
-    if (!h) QN_FAIL(-1, "null handle");
+    if (!h) QS_FAIL(-1, "null handle");
     QS_ON_DEVICE(h);
     const int C = h->o + 1;
     double buf[2 * 256 + 2];
-    QN_HIP(hipStreamSynchronize(h->stream));
-    QN_HIP(hipMemcpy(buf, QN_STAT(h, h->cur), (size_t)(2 * C + 2) * sizeof(double), hipMemcpyDeviceToHost));
+    QS_HIP(hipStreamSynchronize(h->stream));
+    QS_HIP(hipMemcpy(buf, QN_STAT(h, h->cur), (size_t)(2 * C + 2) * sizeof(double), hipMemcpyDeviceToHost));
     for (int c = 0; c < h->o; c++) { if (obs_mean) obs_mean[c] = buf[c]; if (obs_var) obs_var[c] = buf[C + c]; }
     if (ret_mean) *ret_mean = buf[h->o];
     if (ret_var) *ret_var = buf[C + h->o];
@@ -293,27 +286,27 @@ static int norm_launch(qs_norm* h, const qs_norm_io& io, int training, int with_
     hipLaunchKernelGGL(k_norm_finish, dim3(h->n_parts), dim3(256), 0, h->stream, io, h->d_ret, h->n, h->o, QN_STAT(h, h->cur), QN_STAT(h, h->cur ^ 1),
                        (const Moments*)h->d_part, h->n_parts, h->rows_per_block, (double)h->n, h->eps, h->clip_obs, h->clip_rew,
                        training, with_obs, with_ret, norm_obs, norm_reward);
-    QN_HIP(hipGetLastError());
+    QS_HIP(hipGetLastError());
     if (training) h->cur ^= 1;
     return 0;
 }
 
 // VecNormalize.returns, stream-ordered (what a snapshot of the wrapper carries next to the statistics)
 int qs_norm_get_returns(qs_norm* h, double* returns) {
-    if (!h || !returns) QN_FAIL(-1, "null argument");
+    if (!h || !returns) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    QN_HIP(hipMemcpyAsync(returns, h->d_ret, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    QS_HIP(hipMemcpyAsync(returns, h->d_ret, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 int qs_norm_set_returns(qs_norm* h, const double* returns) {
-    if (!h || !returns) QN_FAIL(-1, "null argument");
+    if (!h || !returns) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    QN_HIP(hipMemcpyAsync(h->d_ret, returns, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    QS_HIP(hipMemcpyAsync(h->d_ret, returns, (size_t)h->n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 
 int qs_norm_dims(const qs_norm* h, int* n_envs, int* obs_dim, int* device) {
-    if (!h) QN_FAIL(-1, "null handle");
+    if (!h) QS_FAIL(-1, "null handle");
     if (n_envs) *n_envs = h->n;
     if (obs_dim) *obs_dim = h->o;
     if (device) *device = h->device;
@@ -322,9 +315,9 @@ int qs_norm_dims(const qs_norm* h, int* n_envs, int* obs_dim, int* device) {
 
 // VecNormalize.reset (vec_normalize.py): returns = 0; obs_rms.update(obs) when training; normalize
 int qs_norm_reset(qs_norm* h, float* obs, int training, int norm_obs) {
-    if (!h || !obs) QN_FAIL(-1, "null argument");
+    if (!h || !obs) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    QN_HIP(hipMemsetAsync(h->d_ret, 0, (size_t)h->n * sizeof(double), h->stream));
+    QS_HIP(hipMemsetAsync(h->d_ret, 0, (size_t)h->n * sizeof(double), h->stream));
     qs_norm_io io;
     memset(&io, 0, sizeof(io));
     io.obs = obs;
@@ -333,9 +326,9 @@ int qs_norm_reset(qs_norm* h, float* obs, int training, int norm_obs) {
 
 // VecNormalize.step_wait on the arrays a step produced (device memory; in place unless io->out_* say where the results go)
 int qs_norm_step_io(qs_norm* h, const qs_norm_io* io, int training, int norm_obs, int norm_reward) {
-    if (!h || !io || !io->obs || !io->rew || !io->done) QN_FAIL(-1, "null argument");
+    if (!h || !io || !io->obs || !io->rew || !io->done) QS_FAIL(-1, "null argument");
     if (io->out_done && (!io->out_obs || !io->out_rew || (io->trunc && !io->out_trunc) || (io->tail_rows && !io->out_tail)))
-        QN_FAIL(-1, "qs_norm_io: out_done set, but not every array that is given has its out_ counterpart");
+        QS_FAIL(-1, "qs_norm_io: out_done set, but not every array that is given has its out_ counterpart");
     QS_ON_DEVICE(h);
     return norm_launch(h, *io, training ? 1 : 0, norm_obs, 1, norm_obs, norm_reward);
 }

@@ -25,6 +25,7 @@ namespace pol {
 constexpr int MAX_OBS = 64, MAX_WIDTH = 256, MAX_LAYERS = QS_POLICY_MAX_HIDDEN + 1;
 constexpr int TILE = 16;                       // environments of one MFMA tile
 constexpr int W_LDS_FLOATS = 12288;            // at most 48 KB of a layer's weights in LDS at a time (wider layers: k-chunks)
+constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // of a gfx950 compute unit
 
 // the layers of one policy and where they lie in its parameter row (torch.nn.utils.parameters_to_vector order: per layer weight
 // [out][in] row-major, then bias [out])
@@ -37,6 +38,39 @@ struct Net {
 QP_HD int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // a layer's k-major LDS image [k][out_pad]: the four k of an MFMA step must fall into four different quarters of the 64 banks
 QP_HD int out_pad(int out) { const int op = round_up(out, TILE); return op % 32 == 16 ? op : op + 16; }
+
+// The sizes of a launch's LDS layout (k_policy, qs_policy.hip; k_actor_critic, qs_ppo.hip), as the host fixes them for the networks that pass
+// through one weight image:
+// act_stride = floats of a wave's row [env][k], w_floats = floats of the weight image, wide = some layer needs more than 4 tiles.
+inline void layout_sizes(const Net* const* nets, int n_nets, int& act_stride, int& w_floats, int& wide) {
+    int widest = 0, w_need = 0;
+    wide = 0;
+    for (int i = 0; i < n_nets; i++) {
+        const Net& net = *nets[i];
+        if (round_up(net.obs_dim, 4) > widest) widest = round_up(net.obs_dim, 4);
+        for (int l = 0; l < net.n_layers; l++) {
+            const int nt = (net.out[l] + TILE - 1) / TILE, need = out_pad(net.out[l]) * round_up(net.in[l], 4);
+            if (nt * TILE > widest) widest = nt * TILE;
+            if (need > w_need) w_need = need;
+            if (nt > 4) wide = 1;
+        }
+    }
+    act_stride = round_up(widest, 64) + 4;        // (stride % 64 == 4: the 16 environments x 4 k of an MFMA step cover the 64 banks once)
+    w_floats = w_need < W_LDS_FLOATS ? round_up(w_need, 4) : W_LDS_FLOATS;
+}
+// row_sets: sets of rows [16][act_stride] per wave (k_policy: 1, the activations; k_actor_critic: 2, the observations as well)
+inline size_t lds_bytes(int w_floats, int waves, int row_sets, int act_stride) {
+    return ((size_t)w_floats + (size_t)waves * row_sets * TILE * act_stride) * sizeof(float);
+}
+// waves of a workgroup: as many as share a weight image (the tiles of one group: a policy's block), fewer while that leaves compute units
+// without a workgroup or the compute unit's LDS too small
+inline int waves_per_workgroup(int tiles_per_group, int groups, int w_floats, int row_sets, int act_stride) {
+    int waves = 4;
+    while (waves > 1 && (waves / 2 >= tiles_per_group || (long long)groups * ((tiles_per_group + waves - 1) / waves) < 256 ||
+                         lds_bytes(w_floats, waves, row_sets, act_stride) > LDS_MAX_BYTES))
+        waves /= 2;
+    return waves;
+}
 
 // fills `net`; returns 0 or writes why not into err
 inline int net_from_desc(const qs_policy_desc& d, Net& net, char* err, size_t err_size) {

@@ -16,28 +16,27 @@
 #include "qs_policy.h"
 #include "qs_host.h"
 
-extern thread_local char qs_g_err[512];   // qs_hip.hip
-#define QP_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
-#define QP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QP_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-
 using namespace qs::pol;
 
-struct qs_policy {
-    qs_policy_desc desc;
-    Net net;
-    int device, n_per, tiles_per_policy, waves, wg_per_policy, act_stride, w_floats, wide;
-    size_t lds_bytes;
-    hipStream_t stream;
-    const float* params;      // the caller's [n_policies][n_params] (kept, not copied)
-};
-
 namespace {
-
 struct PolicyArgs {
     const float* obs; const float* params; const float* eps; const float* log_std;
     float* actions; float* mean_out; float* log_prob;
     int n_per, tiles_per_policy, wg_per_policy, act_stride, w_floats;
 };
+}  // namespace
+
+struct qs_policy {
+    qs_policy_desc desc;
+    Net net;
+    int device, n_per, tiles_per_policy, waves, wg_per_policy, act_stride, w_floats;
+    size_t lds_bytes;
+    void (*kernel)(Net, PolicyArgs);   // k_policy<4> or k_policy<16>, chosen at create
+    hipStream_t stream;
+    const float* params;      // the caller's [n_policies][n_params] (kept, not copied)
+};
+
+namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // a wave's LDS rows are written by some of its lanes and read by others: LDS serves one wave's accesses in order, the compiler must keep them so
@@ -131,38 +130,25 @@ __global__ __launch_bounds__(256) void k_policy(Net net, PolicyArgs a) {
 extern "C" {
 
 int qs_policy_create(const qs_policy_desc* d, int device, qs_policy** out) {
-    if (!d || !out) QP_FAIL(-1, "null argument");
+    if (!d || !out) QS_FAIL(-1, "null argument");
     Net net;
     if (net_from_desc(*d, net, qs_g_err, sizeof(qs_g_err))) return -1;
-    int ndev = 0;
-    hipError_t derr = hipGetDeviceCount(&ndev);
-    if (derr != hipSuccess || ndev <= 0) QP_FAIL(-3, "no HIP device available: this library has no CPU path");
-    if (device < 0 || device >= ndev) QP_FAIL(-3, "HIP device %d out of range (%d visible)", device, ndev);
+    if (int rc = qs_check_device(device)) return rc;
     qs_policy* h = new (std::nothrow) qs_policy();
-    if (!h) QP_FAIL(-4, "out of host memory");
+    if (!h) QS_FAIL(-4, "out of host memory");
     memset(h, 0, sizeof(*h));
     h->desc = *d; h->net = net; h->device = device;
     h->n_per = d->n_envs / d->n_policies;
     h->tiles_per_policy = (h->n_per + TILE - 1) / TILE;
-    // waves of a workgroup: as many as share a policy, fewer while that leaves compute units without a workgroup
-    int waves = 4;
-    while (waves > 1 && (waves / 2 >= h->tiles_per_policy || (long long)d->n_policies * ((h->tiles_per_policy + waves - 1) / waves) < 256)) waves /= 2;
-    h->waves = waves;
-    h->wg_per_policy = (h->tiles_per_policy + waves - 1) / waves;
-    int widest = round_up(net.obs_dim, 4), w_need = 0;
-    h->wide = 0;
-    for (int l = 0; l < net.n_layers; l++) {
-        const int nt = (net.out[l] + TILE - 1) / TILE, need = out_pad(net.out[l]) * round_up(net.in[l], 4);
-        if (nt * TILE > widest) widest = nt * TILE;
-        if (need > w_need) w_need = need;
-        if (nt > 4) h->wide = 1;
-    }
-    h->act_stride = round_up(widest, 64) + 4;     // (stride % 64 == 4: the 16 environments x 4 k of an MFMA step cover the 64 banks once)
-    h->w_floats = w_need < W_LDS_FLOATS ? round_up(w_need, 4) : W_LDS_FLOATS;
-    h->lds_bytes = ((size_t)h->w_floats + (size_t)waves * TILE * h->act_stride) * sizeof(float);
+    const Net* nets[1] = {&h->net};
+    int wide;
+    layout_sizes(nets, 1, h->act_stride, h->w_floats, wide);
+    h->waves = waves_per_workgroup(h->tiles_per_policy, d->n_policies, h->w_floats, 1, h->act_stride);
+    h->wg_per_policy = (h->tiles_per_policy + h->waves - 1) / h->waves;
+    h->lds_bytes = lds_bytes(h->w_floats, h->waves, 1, h->act_stride);
+    h->kernel = wide ? k_policy<16> : k_policy<4>;
     DeviceGuard guard(device);
-    hipError_t e = h->wide ? hipFuncSetAttribute((const void*)k_policy<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)
-                           : hipFuncSetAttribute((const void*)k_policy<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+    hipError_t e = hipFuncSetAttribute((const void*)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) { snprintf(qs_g_err, sizeof(qs_g_err), "hipFuncSetAttribute(%zu bytes of LDS) failed: %s", h->lds_bytes, hipGetErrorString(e)); delete h; return -2; }
     *out = h;
     return 0;
@@ -175,29 +161,28 @@ void qs_policy_destroy(qs_policy* h) {
     delete h;
 }
 
-int qs_policy_set_stream(qs_policy* h, void* s) { if (!h) QP_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_policy_set_stream(qs_policy* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
 
-int qs_policy_param_count(const qs_policy* h) { if (!h) QP_FAIL(-1, "null handle"); return h->net.n_params; }
+int qs_policy_param_count(const qs_policy* h) { if (!h) QS_FAIL(-1, "null handle"); return h->net.n_params; }
 
 int qs_policy_set_params(qs_policy* h, const float* dev_params) {
-    if (!h || !dev_params) QP_FAIL(-1, "null argument");
+    if (!h || !dev_params) QS_FAIL(-1, "null argument");
     h->params = dev_params;
     return 0;
 }
 
 int qs_policy_act(qs_policy* h, const float* obs, const float* eps, const float* log_std, float* actions, float* mean_out, float* log_prob) {
-    if (!h || !obs || !actions) QP_FAIL(-1, "null argument (handle, obs and actions are required)");
-    if (!h->params) QP_FAIL(-1, "qs_policy_act before qs_policy_set_params");
-    if (eps && !log_std) QP_FAIL(-1, "eps given without log_std");
-    if (log_prob && !eps) QP_FAIL(-1, "log_prob asked for without eps");
+    if (!h || !obs || !actions) QS_FAIL(-1, "null argument (handle, obs and actions are required)");
+    if (!h->params) QS_FAIL(-1, "qs_policy_act before qs_policy_set_params");
+    if (eps && !log_std) QS_FAIL(-1, "eps given without log_std");
+    if (log_prob && !eps) QS_FAIL(-1, "log_prob asked for without eps");
     QS_ON_DEVICE(h);
     PolicyArgs a;
     a.obs = obs; a.params = h->params; a.eps = eps; a.log_std = log_std; a.actions = actions; a.mean_out = mean_out; a.log_prob = log_prob;
     a.n_per = h->n_per; a.tiles_per_policy = h->tiles_per_policy; a.wg_per_policy = h->wg_per_policy; a.act_stride = h->act_stride; a.w_floats = h->w_floats;
     const dim3 grid((unsigned)(h->desc.n_policies * h->wg_per_policy)), block(64 * h->waves);
-    if (h->wide) hipLaunchKernelGGL(k_policy<16>, grid, block, h->lds_bytes, h->stream, h->net, a);
-    else hipLaunchKernelGGL(k_policy<4>, grid, block, h->lds_bytes, h->stream, h->net, a);
-    QP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(h->kernel, grid, block, h->lds_bytes, h->stream, h->net, a);
+    QS_HIP(hipGetLastError());
     return 0;
 }
 

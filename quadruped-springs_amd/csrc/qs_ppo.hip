@@ -21,33 +21,31 @@
 #include "qs_ppo.h"
 #include "qs_host.h"
 
-extern thread_local char qs_g_err[512];   // qs_hip.hip
-#define QA_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
-#define QA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QA_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-
 using namespace qs::pol;
 namespace ppo = qs::ppo;
 
-struct qs_ac {
-    qs_policy_desc actor_desc, critic_desc;
-    Net actor, critic;
-    int device, n, tiles, waves, act_stride, w_floats, wide;
-    size_t lds_bytes, lds_bytes_one;   // of a launch with `waves` waves / with one wave (masked)
-    hipStream_t stream;
-    const float* actor_params;         // the caller's arrays (kept, not copied)
-    const float* critic_params;
-};
-
 namespace {
-
-constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // of a gfx950 compute unit
-
 struct AcArgs {
     const float* obs; const float* actor_params; const float* critic_params; const float* eps; const float* log_std;
     float* env_actions; float* obs_row; float* action_row; float* value_row; float* log_prob_row;   // collect
     const uint8_t* mask; float* values_out; float* rewards; float gamma;                            // critic only
     int n, tiles, act_stride, w_floats;
 };
+typedef void (*AcKernel)(Net, Net, AcArgs);
+}  // namespace
+
+struct qs_ac {
+    qs_policy_desc actor_desc, critic_desc;
+    Net actor, critic;
+    int device, n, tiles, waves, act_stride, w_floats;
+    size_t lds_bytes, lds_bytes_one;   // of a launch with `waves` waves / with one wave (masked)
+    AcKernel k_collect, k_critic;      // k_actor_critic<4 or 16, true / false>, chosen at create
+    hipStream_t stream;
+    const float* actor_params;         // the caller's arrays (kept, not copied)
+    const float* critic_params;
+};
+
+namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // a wave's LDS rows are written by some of its lanes and read by others: LDS serves one wave's accesses in order, the compiler must keep them so
@@ -186,14 +184,12 @@ __global__ __launch_bounds__(256) void k_gae(const float* __restrict__ rewards, 
     }
 }
 
-template <bool ACTOR>
-int launch(qs_ac* h, const AcArgs& a, bool one_wave) {
+int launch(qs_ac* h, AcKernel kernel, const AcArgs& a, bool one_wave) {
     const int waves = one_wave ? 1 : h->waves;
     const size_t lds = one_wave ? h->lds_bytes_one : h->lds_bytes;
     const dim3 grid((unsigned)((h->tiles + waves - 1) / waves)), block(64 * waves);
-    if (h->wide) hipLaunchKernelGGL((k_actor_critic<16, ACTOR>), grid, block, lds, h->stream, h->actor, h->critic, a);
-    else hipLaunchKernelGGL((k_actor_critic<4, ACTOR>), grid, block, lds, h->stream, h->actor, h->critic, a);
-    QA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, h->actor, h->critic, a);
+    QS_HIP(hipGetLastError());
     return 0;
 }
 
@@ -210,47 +206,29 @@ AcArgs base_args(const qs_ac* h, const float* obs) {
 extern "C" {
 
 int qs_ac_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int device, qs_ac** out) {
-    if (!actor || !critic || !out) QA_FAIL(-1, "null argument");
+    if (!actor || !critic || !out) QS_FAIL(-1, "null argument");
     Net na, nc;
     if (net_from_desc(*actor, na, qs_g_err, sizeof(qs_g_err))) return -1;
     if (net_from_desc(*critic, nc, qs_g_err, sizeof(qs_g_err))) return -1;
     if (ppo::check_pair(*actor, *critic, qs_g_err, sizeof(qs_g_err))) return -1;
-    int ndev = 0;
-    hipError_t derr = hipGetDeviceCount(&ndev);
-    if (derr != hipSuccess || ndev <= 0) QA_FAIL(-3, "no HIP device available: this library has no CPU path");
-    if (device < 0 || device >= ndev) QA_FAIL(-3, "HIP device %d out of range (%d visible)", device, ndev);
+    if (int rc = qs_check_device(device)) return rc;
     qs_ac* h = new (std::nothrow) qs_ac();
-    if (!h) QA_FAIL(-4, "out of host memory");
+    if (!h) QS_FAIL(-4, "out of host memory");
     memset(h, 0, sizeof(*h));
     h->actor_desc = *actor; h->critic_desc = *critic; h->actor = na; h->critic = nc; h->device = device;
     h->n = actor->n_envs;
     h->tiles = (h->n + TILE - 1) / TILE;
-    int widest = round_up(na.obs_dim, 4), w_need = 0;
-    for (const Net* net : {&h->actor, &h->critic})
-        for (int l = 0; l < net->n_layers; l++) {
-            const int nt = (net->out[l] + TILE - 1) / TILE, need = out_pad(net->out[l]) * round_up(net->in[l], 4);
-            if (nt * TILE > widest) widest = nt * TILE;
-            if (need > w_need) w_need = need;
-            if (nt > 4) h->wide = 1;
-        }
-    h->act_stride = round_up(widest, 64) + 4;     // (stride % 64 == 4: the 16 environments x 4 k of an MFMA step cover the 64 banks once)
-    h->w_floats = w_need < W_LDS_FLOATS ? round_up(w_need, 4) : W_LDS_FLOATS;
-    const auto lds_of = [h](int w) { return ((size_t)h->w_floats + (size_t)w * 2 * TILE * h->act_stride) * sizeof(float); };
-    // waves of a workgroup: as many as share the weights, fewer while that leaves compute units without a workgroup or LDS too small
-    int waves = 4;
-    while (waves > 1 && (waves / 2 >= h->tiles || (h->tiles + waves - 1) / waves < 256 || lds_of(waves) > LDS_MAX_BYTES)) waves /= 2;
-    h->waves = waves;
-    h->lds_bytes = lds_of(waves); h->lds_bytes_one = lds_of(1);
+    const Net* nets[2] = {&h->actor, &h->critic};
+    int wide;
+    layout_sizes(nets, 2, h->act_stride, h->w_floats, wide);
+    h->waves = waves_per_workgroup(h->tiles, 1, h->w_floats, 2, h->act_stride);
+    h->lds_bytes = lds_bytes(h->w_floats, h->waves, 2, h->act_stride); h->lds_bytes_one = lds_bytes(h->w_floats, 1, 2, h->act_stride);
+    h->k_collect = wide ? k_actor_critic<16, true> : k_actor_critic<4, true>;
+    h->k_critic = wide ? k_actor_critic<16, false> : k_actor_critic<4, false>;
     DeviceGuard guard(device);
-    hipError_t e = hipSuccess;
     const int lds = (int)h->lds_bytes;            // (the largest launch; a one-wave launch needs less)
-    if (h->wide) {
-        e = hipFuncSetAttribute((const void*)k_actor_critic<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_actor_critic<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    } else {
-        e = hipFuncSetAttribute((const void*)k_actor_critic<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_actor_critic<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
+    hipError_t e = hipFuncSetAttribute((const void*)h->k_collect, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)h->k_critic, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) { snprintf(qs_g_err, sizeof(qs_g_err), "hipFuncSetAttribute(%zu bytes of LDS) failed: %s", h->lds_bytes, hipGetErrorString(e)); delete h; return -2; }
     *out = h;
     return 0;
@@ -263,10 +241,10 @@ void qs_ac_destroy(qs_ac* h) {
     delete h;
 }
 
-int qs_ac_set_stream(qs_ac* h, void* s) { if (!h) QA_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_ac_set_stream(qs_ac* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
 
 int qs_ac_set_params(qs_ac* h, const float* actor_params, const float* critic_params) {
-    if (!h || !actor_params || !critic_params) QA_FAIL(-1, "null argument");
+    if (!h || !actor_params || !critic_params) QS_FAIL(-1, "null argument");
     h->actor_params = actor_params; h->critic_params = critic_params;
     return 0;
 }
@@ -274,40 +252,40 @@ int qs_ac_set_params(qs_ac* h, const float* actor_params, const float* critic_pa
 int qs_ac_collect(qs_ac* h, const float* obs, const float* eps, const float* log_std, float* env_actions, float* obs_row, float* action_row,
                   float* value_row, float* log_prob_row) {
     if (!h || !obs || !eps || !log_std || !env_actions || !obs_row || !action_row || !value_row || !log_prob_row)
-        QA_FAIL(-1, "null argument (qs_ac_collect needs every pointer; eps is required: a collected step is a sample)");
-    if (!h->actor_params) QA_FAIL(-1, "qs_ac_collect before qs_ac_set_params");
+        QS_FAIL(-1, "null argument (qs_ac_collect needs every pointer; eps is required: a collected step is a sample)");
+    if (!h->actor_params) QS_FAIL(-1, "qs_ac_collect before qs_ac_set_params");
     QS_ON_DEVICE(h);
     AcArgs a = base_args(h, obs);
     a.eps = eps; a.log_std = log_std; a.env_actions = env_actions; a.obs_row = obs_row; a.action_row = action_row; a.value_row = value_row;
     a.log_prob_row = log_prob_row;
-    return launch<true>(h, a, false);
+    return launch(h, h->k_collect, a, false);
 }
 
 int qs_ac_values(qs_ac* h, const float* obs, const uint8_t* mask, float* values_out) {
-    if (!h || !obs || !values_out) QA_FAIL(-1, "null argument (handle, obs and values_out are required)");
-    if (!h->critic_params) QA_FAIL(-1, "qs_ac_values before qs_ac_set_params");
+    if (!h || !obs || !values_out) QS_FAIL(-1, "null argument (handle, obs and values_out are required)");
+    if (!h->critic_params) QS_FAIL(-1, "qs_ac_values before qs_ac_set_params");
     QS_ON_DEVICE(h);
     AcArgs a = base_args(h, obs);
     a.mask = mask; a.values_out = values_out;
-    return launch<false>(h, a, mask != nullptr);
+    return launch(h, h->k_critic, a, mask != nullptr);
 }
 
 int qs_ac_bootstrap(qs_ac* h, const float* terminal_obs, const uint8_t* truncated, float gamma, float* rewards_inout) {
-    if (!h || !terminal_obs || !truncated || !rewards_inout) QA_FAIL(-1, "null argument");
-    if (!h->critic_params) QA_FAIL(-1, "qs_ac_bootstrap before qs_ac_set_params");
+    if (!h || !terminal_obs || !truncated || !rewards_inout) QS_FAIL(-1, "null argument");
+    if (!h->critic_params) QS_FAIL(-1, "qs_ac_bootstrap before qs_ac_set_params");
     QS_ON_DEVICE(h);
     AcArgs a = base_args(h, terminal_obs);
     a.mask = truncated; a.rewards = rewards_inout; a.gamma = gamma;
-    return launch<false>(h, a, true);
+    return launch(h, h->k_critic, a, true);
 }
 
 int qs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const uint8_t* last_dones, int T, int N,
            float gamma, float lambda, float* advantages, float* returns, void* hip_stream) {
-    if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns) QA_FAIL(-1, "null argument");
-    if (T <= 0 || N <= 0) QA_FAIL(-1, "qs_gae: T = %d and N = %d must be positive", T, N);
+    if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns) QS_FAIL(-1, "null argument");
+    if (T <= 0 || N <= 0) QS_FAIL(-1, "qs_gae: T = %d and N = %d must be positive", T, N);
     hipLaunchKernelGGL(k_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, rewards, values, episode_starts, last_values,
                        last_dones, T, N, gamma, lambda, advantages, returns);
-    QA_HIP(hipGetLastError());
+    QS_HIP(hipGetLastError());
     return 0;
 }
 

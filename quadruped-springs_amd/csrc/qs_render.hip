@@ -10,10 +10,6 @@
 #include "qs_render.h"
 #include "qs_host.h"
 
-extern thread_local char qs_g_err[512];   // qs_hip.hip
-#define QR_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
-#define QR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QR_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-
 namespace {
 using namespace qs::rnd;
 
@@ -79,12 +75,12 @@ __global__ __launch_bounds__(TILE * TILE) void k_render(RenderSrc src, CamSetup 
 }
 
 int check_args(int m, const qs_camera* cam, int width, int height, const uint32_t* rgba) {
-    if (m < 0) QR_FAIL(-1, "m = %d must not be negative", m);
-    if (!cam) QR_FAIL(-1, "null camera");
-    if (width < 1 || width > 8192 || height < 1 || height > 8192) QR_FAIL(-1, "image size %d x %d outside [1, 8192]", width, height);
-    if (!rgba) QR_FAIL(-1, "null rgba");
-    if (!(cam->fov_deg > 0.0f && cam->fov_deg < 180.0f)) QR_FAIL(-1, "fov_deg = %g outside (0, 180)", (double)cam->fov_deg);
-    if (!(cam->near_clip > 0.0f && cam->near_clip < cam->far_clip)) QR_FAIL(-1, "need 0 < near_clip < far_clip (got %g, %g)", (double)cam->near_clip, (double)cam->far_clip);
+    if (m < 0) QS_FAIL(-1, "m = %d must not be negative", m);
+    if (!cam) QS_FAIL(-1, "null camera");
+    if (width < 1 || width > 8192 || height < 1 || height > 8192) QS_FAIL(-1, "image size %d x %d outside [1, 8192]", width, height);
+    if (!rgba) QS_FAIL(-1, "null rgba");
+    if (!(cam->fov_deg > 0.0f && cam->fov_deg < 180.0f)) QS_FAIL(-1, "fov_deg = %g outside (0, 180)", (double)cam->fov_deg);
+    if (!(cam->near_clip > 0.0f && cam->near_clip < cam->far_clip)) QS_FAIL(-1, "need 0 < near_clip < far_clip (got %g, %g)", (double)cam->near_clip, (double)cam->far_clip);
     return 0;
 }
 
@@ -98,7 +94,7 @@ int launch(const RenderSrc& src, const qs_camera* cam, int m, int width, int hei
     for (int m0 = 0; m0 < m; m0 += (int)per) {
         const int n = (int)(m - m0 < per ? m - m0 : per);
         hipLaunchKernelGGL(k_render, dim3((unsigned)tiles, n), dim3(TILE * TILE), 0, stream, src, cs, tx, m0, rgba, depth, seg);
-        QR_HIP(hipGetLastError());
+        QS_HIP(hipGetLastError());
     }
     return 0;
 }
@@ -108,9 +104,9 @@ int launch(const RenderSrc& src, const qs_camera* cam, int m, int width, int hei
 extern "C" {
 
 int qs_render(qs_handle* h, const int32_t* env_ids, int m, const qs_camera* cam, int width, int height, uint32_t* rgba, float* depth, int32_t* seg) {
-    if (!h) QR_FAIL(-1, "null handle");
+    if (!h) QS_FAIL(-1, "null handle");
     if (int rc = check_args(m, cam, width, height, rgba)) return rc;
-    if (m > 0 && !env_ids) QR_FAIL(-1, "null env_ids");
+    if (m > 0 && !env_ids) QS_FAIL(-1, "null env_ids");
     if (m == 0) return 0;
     QsRenderView v;
     qs_render_view(h, &v);
@@ -126,7 +122,7 @@ int qs_render(qs_handle* h, const int32_t* env_ids, int m, const qs_camera* cam,
 int qs_render_states(const float* states, const float* params, int m, const qs_camera* cam, int width, int height, uint32_t* rgba, float* depth,
                      int32_t* seg, void* stream) {
     if (int rc = check_args(m, cam, width, height, rgba)) return rc;
-    if (m > 0 && !states) QR_FAIL(-1, "null states");
+    if (m > 0 && !states) QS_FAIL(-1, "null states");
     if (m == 0) return 0;
     RenderSrc src;
     src.st = states; src.st_stride = QS_STATE_DIM;

@@ -12,10 +12,6 @@
 #include "qs_snapshot.h"
 #include "qs_host.h"
 
-extern thread_local char qs_g_err[512];   // qs_hip.hip
-#define QSN_FAIL(code, ...) do { snprintf(qs_g_err, sizeof(qs_g_err), __VA_ARGS__); return (code); } while (0)
-#define QSN_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) QSN_FAIL(-2, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
-
 namespace {
 using namespace qs::snap;
 enum { WAVES = 4 };
@@ -66,7 +62,7 @@ unsigned grid_of(int n) { return (unsigned)((n + WAVES - 1) / WAVES); }
 extern "C" {
 
 int qs_snapshot_info(const qs_handle* h, struct qs_snapshot_info* out) {
-    if (!h || !out) QSN_FAIL(-1, "null argument");
+    if (!h || !out) QS_FAIL(-1, "null argument");
     QsSnapshotView v;
     qs_snapshot_view(const_cast<qs_handle*>(h), &v);
     const qs_config& c = *v.cfg;
@@ -81,39 +77,39 @@ int qs_snapshot_info(const qs_handle* h, struct qs_snapshot_info* out) {
 }
 
 int qs_snapshot(qs_handle* h, const uint8_t* mask, float* rows) {
-    if (!h || !rows) QSN_FAIL(-1, "null argument");
-    if ((uintptr_t)rows % 16 != 0) QSN_FAIL(-1, "qs_snapshot: rows must start on 16 bytes");
+    if (!h || !rows) QS_FAIL(-1, "null argument");
+    if ((uintptr_t)rows % 16 != 0) QS_FAIL(-1, "qs_snapshot: rows must start on 16 bytes");
     QsSnapshotView v;
     qs_snapshot_view(h, &v);
     DeviceGuard guard(v.device);
     hipLaunchKernelGGL(k_snapshot, dim3(grid_of(v.cfg->n_envs)), dim3(WAVES * WAVE), 0, v.stream, arrays_of(v), v.cfg->n_envs, v.cfg->obs_dim, mask, rows);
-    QSN_HIP(hipGetLastError());
+    QS_HIP(hipGetLastError());
     return 0;
 }
 
 int qs_restore(qs_handle* h, const uint8_t* mask, const float* rows) {
-    if (!h || !rows) QSN_FAIL(-1, "null argument");
-    if ((uintptr_t)rows % 16 != 0) QSN_FAIL(-1, "qs_restore: rows must start on 16 bytes");
+    if (!h || !rows) QS_FAIL(-1, "null argument");
+    if ((uintptr_t)rows % 16 != 0) QS_FAIL(-1, "qs_restore: rows must start on 16 bytes");
     QsSnapshotView v;
     qs_snapshot_view(h, &v);
     DeviceGuard guard(v.device);
     hipLaunchKernelGGL(k_restore, dim3(grid_of(v.cfg->n_envs)), dim3(WAVES * WAVE), 0, v.stream, arrays_of(v), v.cfg->n_envs, v.cfg->obs_dim, mask, rows,
                        v.la_K > 0 ? v.la_cur : nullptr, v.la_K > 0 ? v.la_handed : nullptr);
-    QSN_HIP(hipGetLastError());
+    QS_HIP(hipGetLastError());
     *v.push_live = 1;   // a push may be pending in the rows: the step launches read the push rows again (until a reset of all)
     return 0;
 }
 
 int qs_fork(qs_handle* h, const int32_t* src_of) {
-    if (!h || !src_of) QSN_FAIL(-1, "null argument");
+    if (!h || !src_of) QS_FAIL(-1, "null argument");
     QsSnapshotView v;
     qs_snapshot_view(h, &v);
     DeviceGuard guard(v.device);
     const int n = v.cfg->n_envs, od = v.cfg->obs_dim;
-    if (!*v.fork_rows) QSN_HIP(hipMalloc(v.fork_rows, (size_t)n * row_floats(od) * sizeof(float)));
+    if (!*v.fork_rows) QS_HIP(hipMalloc(v.fork_rows, (size_t)n * row_floats(od) * sizeof(float)));
     hipLaunchKernelGGL(k_fork_gather, dim3(grid_of(n)), dim3(WAVES * WAVE), 0, v.stream, arrays_of(v), n, od, src_of, *v.fork_rows, v.fork_refused);
     hipLaunchKernelGGL(k_fork, dim3(grid_of(n)), dim3(WAVES * WAVE), 0, v.stream, arrays_of(v), n, od, src_of, (const float*)*v.fork_rows);
-    QSN_HIP(hipGetLastError());
+    QS_HIP(hipGetLastError());
     return 0;
 }
 

@@ -48,6 +48,14 @@ def act(desc, params, obs, eps=None, log_std=None):
     return actions, mean, lp
 
 
+def layout(desc, critic=None):
+    """(act_stride, w_floats, wide, waves, LDS bytes, LDS bytes of a one-wave launch) of k_policy for `desc`, of k_actor_critic with a critic"""
+    out = (C.c_int * 6)()
+    rc = _load().qsepol_layout(C.byref(desc), None if critic is None else C.byref(critic), 1 if critic is None else 2, out)
+    assert rc == 0, rc
+    return tuple(out)
+
+
 def tanh(x):
     x = np.ascontiguousarray(x, np.float32)
     y = np.zeros_like(x)

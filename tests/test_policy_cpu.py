@@ -72,6 +72,25 @@ def test_five_hidden_layers_are_refused():
         emu_policy.param_count(d5)
 
 
+# The LDS layout of a launch of k_policy / k_actor_critic as csrc/qs_policy.h sizes it: (obs_dim, net_arch, action_dim, critic's net_arch or None
+# for k_policy, N, policies) -> act_stride, w_floats, wide, waves, LDS bytes, LDS bytes of a one-wave launch (None: not stated).
+# 48-256-4 is the smallest net with a k-chunked layer (272 x 48 = 13 056 floats, above 12 288).
+LAYOUTS = [
+    ((28, (64, 64), 6, None, 8192, 1), (68, 5120, 0, 2, 29184, None)),
+    ((28, (64, 64), 6, None, 16400, 1), (68, 5120, 0, 4, 37888, None)),
+    ((28, (64, 64), 6, None, 8192, 128), (68, 5120, 0, 2, 29184, None)),
+    ((28, (64, 64), 6, None, 40, 2), (68, 5120, 0, 1, 24832, None)),
+    ((28, (), 6, None, 64, 1), (68, 448, 0, None, None, None)),
+    ((30, (33, 7), 5, None, 64, 1), (68, 1536, 0, None, None, None)),
+    ((64, (256, 200, 256), 12, None, 64, 1), (260, 12288, 1, None, None, None)),
+    ((48, (256,), 4, None, 16400, 1), (260, 12288, 1, 4, 115712, None)),
+    ((48, (256,), 4, None, 100, 1), (260, 12288, 1, 1, 65792, None)),
+    ((28, (64, 64), 6, (64, 64), 8192, 1), (68, 5120, 0, 2, 37888, 29184)),
+    ((28, (64, 64), 6, (64, 64), 16400, 1), (68, 5120, 0, 4, 55296, 29184)),
+    ((48, (256,), 4, (64,), 16400, 1), (260, 12288, 1, 2, 115712, 82432)),     # (4 waves would need 182 272 B, above the 160 KB of a compute unit)
+]
+
+
 def test_param_count_is_parameters_to_vector():
     import torch
     net = torch.nn.Sequential(torch.nn.Linear(28, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 6))
@@ -79,6 +98,12 @@ def test_param_count_is_parameters_to_vector():
     n = torch.nn.utils.parameters_to_vector(net.parameters()).numel()
     assert emu_policy.param_count(desc_of(kw, 16)) == n == P.param_count(28, 6, (64, 64)) == 28 * 64 + 64 + 64 * 64 + 64 + 64 * 6 + 6
     assert emu_policy.param_count(desc_of(dict(kw, net_arch=(), bias=False), 16)) == 28 * 6
+    # ... and the LDS image the same descriptors are given
+    for (obs_dim, arch, action_dim, vf_arch, n, n_pol), want in LAYOUTS:
+        ka = dict(kw, obs_dim=obs_dim, action_dim=action_dim, net_arch=arch, n_policies=n_pol)
+        critic = None if vf_arch is None else desc_of(dict(ka, action_dim=1, net_arch=vf_arch), n)
+        got = emu_policy.layout(desc_of(ka, n), critic)
+        assert all(w is None or g == w for g, w in zip(got, want)), (obs_dim, arch, action_dim, vf_arch, n, n_pol, got, want)
 
 
 # ---- 2. the host emulation against float64, under the derived bound
