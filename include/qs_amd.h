@@ -457,6 +457,42 @@ int qs_ac_bootstrap(qs_ac* h, const float* terminal_obs, const uint8_t* truncate
 int qs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values, const uint8_t* last_dones, int T, int N,
            float gamma, float lambda, float* advantages, float* returns, void* hip_stream);
 
+/* ---- The PPO update on the device (stable_baselines3 1.5 as remembered: PPO.train's minibatch -- evaluate_actions, the clipped loss,
+ * loss.backward, clip_grad_norm_, Adam.step).  The arithmetic, its roundings and its summation order are csrc/qs_ppo_train.h.  For the
+ * policies a qs_ac has, narrowed: obs_dim <= 64, at most 2 hidden layers per network, every width and action_dim <= 64, biases on every
+ * layer, no squash; clip_range_vf is not supported.  Every call is stream-ordered, waits for nothing and allocates nothing. */
+typedef struct qs_ppo qs_ppo;
+typedef struct qs_ppo_hyper {
+    float clip_range, ent_coef, vf_coef;
+    float max_grad_norm;             /* 3e38 for none */
+    int32_t normalize_advantage;     /* skipped for a minibatch of one sample */
+    int32_t reserved;
+    double lr, beta_one, beta_two, adam_eps;   /* torch.optim.Adam(lr, betas, eps); no weight decay, no amsgrad */
+} qs_ppo_hyper;
+enum { QS_PPO_STAT_POLICY_LOSS = 0, QS_PPO_STAT_VALUE_LOSS = 1, QS_PPO_STAT_ENTROPY_LOSS = 2, QS_PPO_STAT_APPROX_KL = 3,
+       QS_PPO_STAT_CLIP_FRACTION = 4, QS_PPO_STAT_GRAD_NORM = 5, QS_PPO_STAT_REFUSED = 6, QS_PPO_STAT_LOSS = 7, QS_PPO_N_STATS = 8 };
+/* PPO.__init__'s share: the two networks (as for a qs_ac; n_envs is not used) and the largest minibatch.  Refuses, with text in
+ * qs_last_error(), what lies outside the limits above and a layout that does not fit a compute unit's LDS; such a handle is never launched. */
+int qs_ppo_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int max_batch, int device, qs_ppo** out);
+void qs_ppo_destroy(qs_ppo* h);
+int qs_ppo_set_stream(qs_ppo* h, void* hip_stream);
+/* policy.parameters() and the optimiser's state: the flat parameter arrays of a qs_ac, log_std [action_dim], and Adam's two moments
+ * [n_actor + n_critic + action_dim] (actor, critic, log_std in that order), all float32 in device memory.  The handle KEEPS THE POINTERS. */
+int qs_ppo_bind(qs_ppo* h, float* actor_params, float* critic_params, float* log_std, float* exp_avg, float* exp_avg_sq);
+/* One minibatch of PPO.train up to and including loss.backward(): rollout_data is taken BY INDEX from the flat [total, ...] rollout arrays
+ * (RolloutBuffer.get's gathers are not materialised): observations [total, obs_dim], actions [total, action_dim], old_log_prob, advantages,
+ * returns [total]; indices [batch] int64.  grad_out [n_actor + n_critic + action_dim] receives the gradient of
+ * policy_loss + ent_coef * entropy_loss + vf_coef * value_loss, stats_out [QS_PPO_N_STATS] the minibatch's statistics (grad_norm is
+ * written by the Adam call).  An index outside [0, total) is not read: its sample contributes nothing, is counted in
+ * stats_out[QS_PPO_STAT_REFUSED] and in the handle's refusal counter. */
+int qs_ppo_grad(qs_ppo* h, const float* observations, const float* actions, const float* old_log_prob, const float* advantages, const float* returns,
+                long long total, const long long* indices, int batch, const qs_ppo_hyper* hyper, float* grad_out, float* stats_out);
+/* clip_grad_norm_(policy.parameters(), max_grad_norm) and optimizer.step(), step = 1, 2, ...: in place on the bound parameters and moments.
+ * grad is what the handle's last gradient call wrote (its sums of squares are the handle's); stats_inout[QS_PPO_STAT_GRAD_NORM] receives the norm before clipping. */
+int qs_ppo_adam(qs_ppo* h, const float* grad, const qs_ppo_hyper* hyper, int step, float* stats_inout);
+/* samples refused since the last call (waits for the handle's stream) */
+int qs_ppo_refusals(qs_ppo* h, unsigned long long* out);
+
 /* ---- Device snapshots: save, restore and fork environments (what pybullet.saveState / restoreState are to the reference's simulator; the CPU
  * oracle's qso_snapshot / qso_restore).  A snapshot is one row of qs_snapshot_info::row_floats floats per environment, in DEVICE memory owned by
  * the caller (16-byte aligned): [the environment's whole record | its push row | its last observation | its terminal observation], layout in
@@ -507,7 +543,7 @@ const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 9
 int qs_abi_version(void);
 

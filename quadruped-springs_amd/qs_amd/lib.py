@@ -21,6 +21,7 @@ EXPORTS = (
     "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
     "qs_ac_create", "qs_ac_destroy", "qs_ac_set_stream", "qs_ac_set_params", "qs_ac_collect", "qs_ac_values", "qs_ac_bootstrap", "qs_gae",
     "qs_snapshot_info", "qs_snapshot", "qs_restore", "qs_fork", "qs_norm_get_returns", "qs_norm_set_returns",
+    "qs_ppo_create", "qs_ppo_destroy", "qs_ppo_set_stream", "qs_ppo_bind", "qs_ppo_grad", "qs_ppo_adam", "qs_ppo_refusals",
 )
 
 
@@ -56,6 +57,15 @@ class QsRack(C.Structure):
     """qs_rack (include/qs_amd.h): the rack of qs_create_ex (Quadruped(on_rack=True))."""
     _fields_ = [("on", C.c_int32), ("anchor_pos", C.c_float * 3), ("anchor_quat", C.c_float * 4)]
 
+
+class QsPpoHyper(C.Structure):
+    """qs_ppo_hyper (include/qs_amd.h): the hyper-parameters of qs_ppo_grad and qs_ppo_adam."""
+    _fields_ = [("clip_range", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float), ("max_grad_norm", C.c_float),
+                ("normalize_advantage", C.c_int32), ("reserved", C.c_int32),
+                ("lr", C.c_double), ("beta_one", C.c_double), ("beta_two", C.c_double), ("adam_eps", C.c_double)]
+
+
+PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm", "refused", "loss")   # QS_PPO_STAT_*
 
 _lib = None
 
@@ -145,6 +155,15 @@ def load():
         lib.qs_fork.argtypes = [vp, vp]
         lib.qs_norm_get_returns.argtypes = [vp, vp]
         lib.qs_norm_set_returns.argtypes = [vp, vp]
+    if hasattr(lib, "qs_ppo_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
+        lib.qs_ppo_create.argtypes = [C.POINTER(QsPolicyDesc), C.POINTER(QsPolicyDesc), i32, i32, C.POINTER(vp)]
+        lib.qs_ppo_destroy.argtypes = [vp]
+        lib.qs_ppo_destroy.restype = None
+        lib.qs_ppo_set_stream.argtypes = [vp, vp]
+        lib.qs_ppo_bind.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.qs_ppo_grad.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, vp, i32, C.POINTER(QsPpoHyper), vp, vp]
+        lib.qs_ppo_adam.argtypes = [vp, vp, C.POINTER(QsPpoHyper), i32, vp]
+        lib.qs_ppo_refusals.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)

@@ -1,6 +1,7 @@
 """PPO with the collection on the device: DeviceActorCritic (actor and critic in ONE HIP launch per collected step, k_actor_critic,
 csrc/qs_ppo.hip), DeviceRolloutBuffer ([T, N, ...] device tensors, GAE in one launch, k_gae) and DevicePPO (SB3's PPO loop: the rollout
-on the device, the update -- SB3's PPO.train -- in torch with autograd).
+on the device; the update -- SB3's PPO.train -- in torch with autograd, or with update="device" in HIP as well: per minibatch the gradient
+by index from the rollout arrays, k_ppo_grad, and clip + Adam in place, k_ppo_adam, csrc/qs_ppo_train.hip).
 
 The parameters live ONCE: one flat float32 tensor per network in `torch.nn.utils.parameters_to_vector` order, which the kernels read in
 place, and torch.nn modules whose Parameters are views into those tensors, which autograd and the optimiser work on.  An optimiser step
@@ -18,6 +19,7 @@ from . import lib as _lib
 from .policy import ACTIVATIONS, MAX_HIDDEN, _to_numpy, layer_shapes, layers_from_state_dict, param_count, state_dict_from_zip
 
 NO_CLIP = 3.0e38
+UPDATE_MAX_HIDDEN, UPDATE_MAX_WIDTH = 2, 64      # what update="device" takes (csrc/qs_ppo_train.h)
 
 
 def _sequential(flat, obs_dim, out_dim, arch, activation):
@@ -298,10 +300,18 @@ class DevicePPO:
     handed buffers (train())."""
 
     def __init__(self, env, policy, n_steps=128, batch_size=None, n_epochs=10, learning_rate=3e-4, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
-                 clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, normalize_advantage=True, seed=0):
+                 clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, target_kl=None, normalize_advantage=True, seed=0, update="torch"):
+        """update: "torch" = PPO.train in torch with autograd (any policy a DeviceActorCritic takes, clip_range_vf); "device" = the same
+        minibatches through qs_ppo_grad / qs_ppo_adam, for at most 2 hidden layers per network, widths and action_dim up to 64,
+        clip_range_vf None and a constant learning_rate and clip_range: anything else raises ValueError here"""
         import torch
         self.torch = torch
         self.env, self.policy = env, policy
+        if update not in ("torch", "device"):
+            raise ValueError(f'update = {update!r} is neither "torch" nor "device"')
+        self.update = update
+        if update == "device":
+            self._check_device_update(policy, learning_rate, clip_range, clip_range_vf)
         if env is not None:
             if (env.num_envs, env.obs_dim, env.action_dim) != (policy.num_envs, policy.obs_dim, policy.action_dim):
                 raise ValueError(f"the environment has (num_envs, obs_dim, action_dim) = {(env.num_envs, env.obs_dim, env.action_dim)}, the policy "
@@ -320,6 +330,9 @@ class DevicePPO:
         self.generator.manual_seed(int(seed))
         self.num_timesteps = 0
         self._last_obs = None
+        self.hp = None
+        if update == "device":
+            self._init_device_update(learning_rate)
         if env is not None:
             T, N = self.n_steps, policy.num_envs
             f32 = dict(dtype=torch.float32, device=self.device)
@@ -378,13 +391,130 @@ class DevicePPO:
         self._ep_ret = c[-1] - t.where(last[-1] >= 0, c.gather(0, last[-1:].clamp(min=0))[0], t.zeros_like(c[-1]))
         return ret_sum, count
 
+    # ---- the update on the device
+    @staticmethod
+    def _check_device_update(policy, learning_rate, clip_range, clip_range_vf):
+        why = None
+        for who, arch in (("actor", policy.net_arch), ("critic", policy.vf_arch)):
+            if len(arch) > UPDATE_MAX_HIDDEN:
+                why = why or f"the {who} has {len(arch)} hidden layers, the device update takes at most {UPDATE_MAX_HIDDEN}"
+            if any(w > UPDATE_MAX_WIDTH for w in arch):
+                why = why or f"the {who}'s widths {tuple(arch)} exceed {UPDATE_MAX_WIDTH} (a layer's weight-gradient tiles stay in registers)"
+        if policy.action_dim > UPDATE_MAX_WIDTH:
+            why = why or f"action_dim = {policy.action_dim} exceeds {UPDATE_MAX_WIDTH}"
+        if clip_range_vf is not None:
+            why = why or f"clip_range_vf = {clip_range_vf!r} is not supported (only None)"
+        if callable(learning_rate) or callable(clip_range):
+            why = why or "learning_rate and clip_range must be constants, not schedules"
+        if why:
+            raise ValueError(f'DevicePPO(update="device"): {why}; update="torch" takes it')
+
+    def _hyper(self):
+        return _lib.QsPpoHyper(float(self.clip_range), float(self.ent_coef), float(self.vf_coef), NO_CLIP if self.max_grad_norm is None else float(self.max_grad_norm),
+                               int(bool(self.normalize_advantage)), 0, float(self.learning_rate), 0.9, 0.999, 1e-5)
+
+    def _init_device_update(self, learning_rate):
+        """Adam's state as two flat tensors over [actor | critic | log_std] (exp_avg, exp_avg_sq), the last gradient (grad), the step count;
+        on a GPU the qs_ppo handle bound to the policy's own parameter memory"""
+        t, pol = self.torch, self.policy
+        self.learning_rate = float(learning_rate)
+        n = pol.actor_params.numel() + pol.critic_params.numel() + pol.action_dim
+        f32 = dict(dtype=t.float32, device=self.device)
+        self.exp_avg, self.exp_avg_sq, self.grad = t.zeros(n, **f32), t.zeros(n, **f32), t.zeros(n, **f32)
+        self._stats = t.zeros(len(_lib.PPO_STATS), **f32)
+        self.adam_step = 0
+        if self.device.type != "cuda":
+            return
+        lib = self.lib = _lib.load()
+
+        def desc(out_dim, arch):
+            return _lib.QsPolicyDesc(pol.num_envs, 1, pol.obs_dim, out_dim, len(arch), (C.c_int32 * 4)(*arch), ACTIVATIONS[pol.activation], 0, 1, -NO_CLIP, NO_CLIP)
+        self.hp = C.c_void_p()
+        _lib.check(lib.qs_ppo_create(C.byref(desc(pol.action_dim, pol.net_arch)), C.byref(desc(1, pol.vf_arch)), self.n_steps * pol.num_envs,
+                                     self.device.index or 0, C.byref(self.hp)))
+        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        _lib.check(lib.qs_ppo_bind(self.hp, p(pol.actor_params), p(pol.critic_params), p(pol.log_std.data), p(self.exp_avg), p(self.exp_avg_sq)))
+
+    def _read_stats(self):
+        """the statistics of the last minibatch as python floats (waits for the device); raises if any minibatch since the last read
+        refused samples (the handle's counter, qs_ppo_refusals, which this read clears)"""
+        out = dict(zip(_lib.PPO_STATS, self._stats.cpu().tolist()))
+        count = C.c_uint64(0)
+        _lib.check(self.lib.qs_ppo_refusals(self.hp, C.byref(count)))
+        if count.value > 0:
+            raise RuntimeError(f"qs_ppo_grad refused {count.value} samples since the last statistics read: indices outside [0, total)")
+        return out
+
+    def grad_minibatch(self, idx):
+        """qs_ppo_grad for the minibatch idx (int64 tensor of indices into the flat [T * N] rollout) -> self.grad, self._stats; on torch's
+        current stream, waits for nothing"""
+        t, buf = self.torch, self.buffer
+        if self.hp is None:
+            raise RuntimeError(f'DevicePPO(update="device") trains on a GPU; this one was built on {self.device} (there is no CPU path)')
+        if idx.dtype != t.int64 or idx.device != self.device or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous int64 tensor on the learner's device")
+        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        self._hy = self._hyper()
+        _lib.check(self.lib.qs_ppo_set_stream(self.hp, C.c_void_p(t.cuda.current_stream(self.device).cuda_stream)))
+        _lib.check(self.lib.qs_ppo_grad(self.hp, p(buf.observations), p(buf.actions), p(buf.log_probs), p(buf.advantages), p(buf.returns),
+                                        buf.n_steps * buf.num_envs, p(idx), idx.numel(), C.byref(self._hy), p(self.grad), p(self._stats)))
+
+    def adam_minibatch(self):
+        """qs_ppo_adam with self.grad: clip_grad_norm_ and optimizer.step() in place on the policy's parameters"""
+        self.adam_step += 1
+        _lib.check(self.lib.qs_ppo_adam(self.hp, C.c_void_p(self.grad.data_ptr()), C.byref(self._hy), self.adam_step, C.c_void_p(self._stats.data_ptr())))
+
+    def _train_device(self):
+        t = self.torch
+        total, bs = self.n_steps * self.policy.num_envs, self.batch_size
+        epochs_run, go_on, ran = 0, True, False
+        for _ in range(self.n_epochs):
+            perm = t.randperm(total, device=self.device, generator=self.generator)     # (DeviceRolloutBuffer.get's, from the same generator)
+            for start in range(0, total, bs):
+                self.grad_minibatch(perm[start:start + bs])
+                ran = True
+                if self.target_kl is not None and self._read_stats()["approx_kl"] > 1.5 * self.target_kl:
+                    go_on = False
+                    break
+                self.adam_minibatch()
+            if not go_on:
+                break
+            epochs_run += 1
+        s = self._read_stats() if ran else {}                             # (n_epochs = 0: nothing ran, every figure is nan)
+        out = {k: s.get(k, float("nan")) for k in ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")}
+        out["grad_norm"] = s.get("grad_norm", float("nan")) if go_on else float("nan")      # (the early stop skips the step that would have measured it)
+        out["n_epochs_run"] = epochs_run
+        return out
+
+    def close(self):
+        """frees the qs_ppo handle (also at garbage collection and at the end of a `with` block)"""
+        if getattr(self, "hp", None):
+            self.lib.qs_ppo_destroy(self.hp)
+            self.hp = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown: the library may be gone already)
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
     # ---- the update
     def train(self):
-        """SB3's PPO.train on self.buffer -> dict(approx_kl, policy_loss, value_loss, entropy_loss, clip_fraction, n_epochs_run) of python
-        floats (the one host synchronisation, at the end; with target_kl one per minibatch, as the early stop needs the value)."""
+        """SB3's PPO.train on self.buffer -> dict(approx_kl, policy_loss, value_loss, entropy_loss, clip_fraction, grad_norm, n_epochs_run)
+        of python floats (the one host synchronisation, at the end; with target_kl one per minibatch, as the early stop needs the value).
+        grad_norm is the last minibatch's norm before clipping (nan if the early stop skipped that step)."""
+        if self.update == "device":
+            return self._train_device()
         t, pol = self.torch, self.policy
         params = pol.parameters()
-        last, epochs_run, go_on = None, 0, True
+        last, epochs_run, go_on, norm = None, 0, True, None
         for _ in range(self.n_epochs):
             for mb in self.buffer.get(self.batch_size, generator=self.generator):
                 values, log_prob, entropy = pol.evaluate_actions(mb["observations"], mb["actions"])
@@ -396,13 +526,13 @@ class DevicePPO:
                     break
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
-                if self.max_grad_norm is not None:
-                    t.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+                norm = t.nn.utils.clip_grad_norm_(params, float("inf") if self.max_grad_norm is None else self.max_grad_norm)
                 self.optimizer.step()
             if not go_on:
                 break
             epochs_run += 1
         out = {k: float(v) for k, v in last.items()}
+        out["grad_norm"] = float(norm) if go_on and norm is not None else float("nan")
         out["n_epochs_run"] = epochs_run
         return out
 
