@@ -279,7 +279,8 @@ enum { QS_COUNTER_SETTLE_SUBSTEPS = 0,      /* settle substeps executed (k_reset
        QS_COUNTER_SELF_NARROW_SUBSTEPS = 5, /* wave-substeps (the last of an env step) whose self-collision broad phase found a calf close
                                                enough to another leg or the trunk to run the link-link tests (of this handle) */
        QS_COUNTER_RESET_STALLS = 6,         /* resets of a handle with reset_lookahead > 0 whose state was not ready: settled in place */
-       QS_COUNTER_LOOKAHEAD_BACKLOG = 7     /* reset states the environments' look-ahead windows lack and no settle lane has taken yet */ };
+       QS_COUNTER_LOOKAHEAD_BACKLOG = 7,    /* reset states the environments' look-ahead windows lack and no settle lane has taken yet */
+       QS_COUNTER_SOLO_PATH_SUBSTEPS = 8    /* of LIMIT_PATH_SUBSTEPS: those of solo waves (qs_solo_waves), which hold up no wave-mate */ };
 int qs_counter(qs_handle* h, int which, uint64_t* value);
 /* The counters 0 .. 6 as they stand at this point of the handle's stream, copied to `dev_out[8]` (DEVICE memory; entry 7 is left alone) by
  * copies enqueued on the stream: nothing is waited for.  For a reader that wants the counters of a region without idling the device in
@@ -302,6 +303,16 @@ int qs_last_step_kernel_ms(qs_handle* h, float* ms);
  * nothing is settled ahead (the settles in progress start over when the lanes come back), resets use up the states that are ready and
  * then settle in place -- results do not change, only when the work is done. */
 int qs_settle_lanes(qs_handle* h, int on);
+/* Solo waves of a handle with look-ahead reset states.  A robot that ends an env step with a non-foot link within `reach` metres of its
+ * contact range is stepped, in the next launch, by a workgroup of its own -- one of `f` extra workgroups at the front of the grid -- next to
+ * fifteen copies of a parked record instead of next to its fifteen wave-mates: the many-rows substeps of its fall then hold up nobody and
+ * skip the common-path solve that only the mates need.  Results do not change, bit for bit; only who computes them.  f = 0 switches them
+ * off, f = -1 keeps the count; f up to 512.  reach <= 0 keeps the current one.  Defaults: QS_SOLO_WAVES / QS_SOLO_REACH in the environment at qs_create, else
+ * 128 workgroups and 0.02 m.  They run only where they fit next to the environments' waves and the settle lanes on otherwise idle SIMDs,
+ * in the one-wave-per-SIMD kernels, with cfg.body_contacts and without rack or soft payload; elsewhere the setting is kept and nothing
+ * happens.  QS_COUNTER_SOLO_PATH_SUBSTEPS / QS_COUNTER_LIMIT_PATH_SUBSTEPS is the share of the many-rows wave-substeps they take.
+ * Fails for f > 0 on a handle without look-ahead states (cfg.reset_lookahead = 0, or QS_RAND_KEEP). */
+int qs_solo_waves(qs_handle* h, int f, float reach);
 /* Per-substep trace tap for ONE environment (evaluation_wrapper.py:14,36-41 set_sub_step_callback; monitor_state.py:66-85):
  * while set, every qs_step writes action_repeat rows of QS_TRACE_DIM floats into `rows` (device memory, caller owned), one per
  * physics substep of environment `env`: sim time, base position 3, quaternion xyzw 4, linear velocity 3, angular velocity 3,

@@ -1557,7 +1557,12 @@ template <class T, bool CONE = false, bool HOT = false, bool SOFT = false, bool 
         // stop, no link on the floor) keep ITS result -- bit for bit what the common-path build gives them in a wave without such a
         // neighbour; only the environments with rare rows take the many-rows solver's.  (Both solvers run for the whole wave: wave votes
         // must not sit under a divergent branch.)
-        if (RACK ? rack : (SOFT || (!HOT && soft))) {
+        // (full build) Nobody is left for it: every environment with an active row has rare rows of its own and takes the many-rows result --
+        // a fallen robot alone in its wave (a solo wave of the step kernel, a partial wave, the one-quad emulation).  The others get what
+        // "nothing to solve" gives them below: all their rows are inactive, delta v = 0 exactly.
+        if (!HOT && !soft && !rack && !T::any(qand(qnot(rare_mine), qor(act_m, any_lim)))) {
+            o.foot_force = zero; s.warm = zero;
+        } else if (RACK ? rack : (SOFT || (!HOT && soft))) {
             if (HOT && !RACK) payload_rows(cfg, Pr, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);      // (a handle without the block does not launch this build)
             if (HOT && RACK) rack_rows(cfg, s, vs, Rx, Ry, Rz, Sm, Ld, blk, pay_c);
             if (cfg.solver_residual_threshold > 0.0f) solve_and_integrate<3, true, true>(cfg, Pr.mu, s, o, rows, Sm, Ld, BK, R, &pay_c);

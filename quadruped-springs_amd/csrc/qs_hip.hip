@@ -46,7 +46,7 @@ __device__ __forceinline__ int tile_extent(const qs_config& cfg, bool store) {
 // load into its store's branch, one memory trip per round again)
 __device__ __forceinline__ void keep_loaded(const float4& v) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); }
 __device__ __forceinline__ void keep_loaded(float v) { asm volatile("" ::"v"(v)); }
-template <int PER> __device__ __forceinline__ void tile_load_rounds(float4* __restrict__ dst, const float4* __restrict__ src, int nenv, int stride4, int per_rt) {
+template <int PER> __device__ __forceinline__ void tile_load_rounds(float4* __restrict__ dst, const float4* __restrict__ src, const float4* __restrict__ park, int nenv, int stride4, int per_rt) {
     constexpr int MAX_PER = QS_REC_END / 4;
     constexpr int ROUNDS = PER > 0 ? (QS_ENVS_PER_WAVE * PER + QS_WAVE - 1) / QS_WAVE : (QS_ENVS_PER_WAVE * MAX_PER + QS_WAVE - 1) / QS_WAVE;
     const int per = PER > 0 ? PER : per_rt, total = QS_ENVS_PER_WAVE * per;
@@ -59,7 +59,10 @@ template <int PER> __device__ __forceinline__ void tile_load_rounds(float4* __re
         // assigned under a condition would send the whole array to scratch)
         const bool in = (PER > 0 && (QS_ENVS_PER_WAVE * PER) % QS_WAVE == 0) || i < total;
         const int e = PER > 0 ? i / PER : (int)(((unsigned)i * inv) >> 20), o = i - e * per;
-        v[r] = src[in ? (e < nenv ? e : 0) * (QS_REC / 4) + o : 0];   /* tail quads replay the tile's first record (never stored) */
+        // tail quads get the handle's parked record -- a robot that hangs in the air and asks for no rare path -- where it has one (`park`;
+        // else they replay the tile's first record); never stored
+        const float4* const from = e < nenv ? src + e * (QS_REC / 4) : park;
+        v[r] = in ? from[o] : src[0];
     }
     if (!(PER > 0 && (QS_ENVS_PER_WAVE * PER) % QS_WAVE == 0)) {
 #pragma unroll
@@ -74,17 +77,28 @@ template <int PER> __device__ __forceinline__ void tile_load_rounds(float4* __re
         }
     }
 }
-__device__ __forceinline__ void tile_load(float* lds, const float* __restrict__ g, int first_env, int n_envs, int extent, int stride = QS_REC_END) {
+__device__ __forceinline__ void tile_load(float* lds, const float* __restrict__ g, int first_env, int n_envs, int extent, int stride = QS_REC_END, const float* __restrict__ parked = nullptr) {
     // Only the leading range [0, extent) of each record is fetched (QS_HOT by default: the info block behind it is written, never read
     // back, by a step).
     const float4* src = reinterpret_cast<const float4*>(g + (size_t)first_env * QS_REC);
     float4* dst = reinterpret_cast<float4*>(lds);
+    const float4* park = parked ? reinterpret_cast<const float4*>(parked) : src;
     const int nenv = min(QS_ENVS_PER_WAVE, n_envs - first_env);
-    if (extent == QS_HOT) tile_load_rounds<QS_HOT / 4>(dst, src, nenv, stride / 4, 0);
-    else if (extent == QS_SETTLE_END) tile_load_rounds<QS_SETTLE_END / 4>(dst, src, nenv, stride / 4, 0);
-    else tile_load_rounds<0>(dst, src, nenv, stride / 4, extent / 4);
+    if (extent == QS_HOT) tile_load_rounds<QS_HOT / 4>(dst, src, park, nenv, stride / 4, 0);
+    else if (extent == QS_SETTLE_END) tile_load_rounds<QS_SETTLE_END / 4>(dst, src, park, nenv, stride / 4, 0);
+    else tile_load_rounds<0>(dst, src, park, nenv, stride / 4, extent / 4);
 }
-template <int PER> __device__ __forceinline__ void tile_store_rounds(float4* __restrict__ dst, const float4* __restrict__ src, int nenv, int stride4, int b4, int per_rt) {
+// the parked record into the LDS slots a 64-lane ballot names (bit 4 e = slot e): the slots of environments that a solo wave steps
+__device__ __forceinline__ void tile_park(float* lds, const float* __restrict__ parked, unsigned long long slots, int extent, int stride) {
+    const float4* src = reinterpret_cast<const float4*>(parked);
+    for (int e = 0; e < QS_ENVS_PER_WAVE; e++) {
+        if (!((slots >> (4 * e)) & 1ull)) continue;
+        float4* dst = reinterpret_cast<float4*>(lds + e * stride);
+        for (int i = threadIdx.x; i < extent / 4; i += QS_WAVE) dst[i] = src[i];
+    }
+}
+// `skip` (a 64-lane ballot, bit 4 e = slot e): records that are not this wave's to store
+template <int PER> __device__ __forceinline__ void tile_store_rounds(float4* __restrict__ dst, const float4* __restrict__ src, int nenv, int stride4, int b4, int per_rt, unsigned long long skip) {
     constexpr int MAX_PER = QS_REC_END / 4;
     constexpr int ROUNDS = PER > 0 ? (QS_ENVS_PER_WAVE * PER + QS_WAVE - 1) / QS_WAVE : (QS_ENVS_PER_WAVE * MAX_PER + QS_WAVE - 1) / QS_WAVE;
     const int per = PER > 0 ? PER : per_rt, total = nenv * per;
@@ -101,22 +115,22 @@ template <int PER> __device__ __forceinline__ void tile_store_rounds(float4* __r
 #pragma unroll
     for (int r = 0; r < ROUNDS; r++) {
         const int i = (int)threadIdx.x + r * QS_WAVE;
-        if (i < total) { const int e = PER > 0 ? i / PER : (int)(((unsigned)i * inv) >> 20), o = i - e * per + b4; dst[e * (QS_REC / 4) + o] = v[r]; }
+        if (i < total) { const int e = PER > 0 ? i / PER : (int)(((unsigned)i * inv) >> 20), o = i - e * per + b4; if (!((skip >> (4 * e)) & 1ull)) dst[e * (QS_REC / 4) + o] = v[r]; }
     }
 }
-__device__ __forceinline__ void tile_store(const float* lds, float* __restrict__ g, int first_env, int n_envs, int begin, int end, int stride = QS_REC_END) {
+__device__ __forceinline__ void tile_store(const float* lds, float* __restrict__ g, int first_env, int n_envs, int begin, int end, int stride = QS_REC_END, unsigned long long skip = 0ull) {
     float4* dst = reinterpret_cast<float4*>(g + (size_t)first_env * QS_REC);
     const float4* src = reinterpret_cast<const float4*>(lds);
     const int nenv = min(QS_ENVS_PER_WAVE, n_envs - first_env);
-    if (begin == QS_RW_BEGIN && end == QS_HOT) tile_store_rounds<(QS_HOT - QS_RW_BEGIN) / 4>(dst, src, nenv, stride / 4, QS_RW_BEGIN / 4, 0);
-    else if (begin == QS_RW_BEGIN && end == QS_SETTLE_END) tile_store_rounds<(QS_SETTLE_END - QS_RW_BEGIN) / 4>(dst, src, nenv, stride / 4, QS_RW_BEGIN / 4, 0);
-    else tile_store_rounds<0>(dst, src, nenv, stride / 4, begin / 4, (end - begin) / 4);
+    if (begin == QS_RW_BEGIN && end == QS_HOT) tile_store_rounds<(QS_HOT - QS_RW_BEGIN) / 4>(dst, src, nenv, stride / 4, QS_RW_BEGIN / 4, 0, skip);
+    else if (begin == QS_RW_BEGIN && end == QS_SETTLE_END) tile_store_rounds<(QS_SETTLE_END - QS_RW_BEGIN) / 4>(dst, src, nenv, stride / 4, QS_RW_BEGIN / 4, 0, skip);
+    else tile_store_rounds<0>(dst, src, nenv, stride / 4, begin / 4, (end - begin) / 4, skip);
 }
 
 // the observation rows of the tile (LDS, QS_MAX_OBS apart) to the caller's rows ([N, od], or [N, od + 2] in the fused layout) and the
 // handle's own copy.  i / od by multiply-shift: exact for i < 16 * 64, od <= 64 with inv = ceil(2^16 / od) (one division per wave
 // instead of two per element).  Batched like the tile moves: the LDS reads of all rounds first, then the stores.
-__device__ __forceinline__ void obs_store(const float* s_obs, int nrow, int od, int first, float* __restrict__ obs_out, bool fused, float* __restrict__ obs_keep) {
+__device__ __forceinline__ void obs_store(const float* s_obs, int nrow, int od, int first, float* __restrict__ obs_out, bool fused, float* __restrict__ obs_keep, unsigned long long skip = 0ull) {
     const unsigned inv = (65536u + (unsigned)od - 1u) / (unsigned)od;
     const int row = fused ? od + 2 : od, total = nrow * od;
     constexpr int ROUNDS = QS_ENVS_PER_WAVE * QS_MAX_OBS / QS_WAVE;
@@ -134,6 +148,7 @@ __device__ __forceinline__ void obs_store(const float* s_obs, int nrow, int od, 
         const int i = (int)threadIdx.x + r * QS_WAVE;
         if (i < total) {
             const int e = (int)(((unsigned)i * inv) >> 16), o = i - e * od;
+            if ((skip >> (4 * e)) & 1ull) continue;
             obs_out[(size_t)(first + e) * row + o] = v[r];
             obs_keep[(size_t)first * od + i] = v[r];
         }
@@ -158,6 +173,8 @@ struct LookAhead {
 // per launch; ctl = the counters in qs_handle::d_stats.  The staging area is split into QS_COHORTS slices whose settles start QS_COHORTS-th
 // of an epoch (= the launches one settle takes) apart, so that a wanted state waits at most epoch / QS_COHORTS launches for a lane.
 #define QS_COHORTS 5
+#define QS_SOLO_DEFAULT 128          // solo waves per launch (qs_solo_waves, QS_SOLO_WAVES)
+#define QS_SOLO_REACH_DEFAULT 0.02f  // ... for robots with a link within this of its contact range [m] (QS_SOLO_REACH)
 #define QS_MAX_SLICE 2048
 struct SettleLanes { float* staging; const int2* stage_jobs; int n_env_waves, slice; int wave0[QS_COHORTS + 1] /* first settle wave of each cohort */,
                      spawn[QS_COHORTS], last[QS_COHORTS], settle_n[QS_COHORTS]; };
@@ -171,13 +188,51 @@ struct TermTail { float* rows; int cap, parity; };
 // where no push can be pending (the host knows: no push set since the last reset of every environment): the step then reads nothing of it.
 struct PushTab { float* rows; };
 enum { QS_PUSH_F = 8, QS_PUSH_REM = 6, QS_PUSH_FRAME = 7 };
+// Solo waves: the first F workgroups of a step launch each step ONE environment -- a robot that the end of the previous step saw close to
+// putting a link on the floor -- next to fifteen copies of the parked record, on a SIMD the launch leaves idle.  Such a robot's many-rows
+// substeps then hold up nobody, and with no wave-mate on the common path they skip that solve (qs_core.h).  Who steps environment e in a
+// launch: its home wave iff moved_rd[e] == 0, solo wave j iff j < min(count, F) and list_rd[j] == e -- exactly one of them, whatever the
+// rule that set the flag says; whoever steps e writes moved_wr[e] (and the list) for the next launch.  Flags alternate between two
+// arrays, lists and their fill counts (CTL_SOLO_CNT) rotate through three: launch i reads [i % 3], fills [(i + 1) % 3], clears the count of
+// [(i + 2) % 3].  F = 0: no solo waves, nothing of this is read or written.
+#define QS_SOLO_MAX 512
+struct SoloWaves { const float* parked;   // the handle's parked record (also the tail quads' of a partial wave); null: none
+                   const int* moved_rd; int* moved_wr; const int* list_rd; int* list_wr; int F, rd, wr, clr; float reach; };
 enum { CTL_SETTLE_SUBSTEPS = 0, CTL_RESETS = 1, CTL_SERVED = 2, CTL_SETTLED = 3, CTL_BACKLOG = 4, CTL_STALLS = 6,
        CTL_R = 8 /* one per cohort */, CTL_TERM_CNT = 8 + QS_COHORTS /* two */, CTL_DEV = 10 + QS_COHORTS /* QS_DEVCTR_*: the rare paths' telemetry */,
        /* (CTL_DEV + 2 .. + 11: the counting builds' counters, qs_core.h, tools/probe_*.py) */
        CTL_PUSH_REFUSED = 22 + QS_COHORTS /* 1 + the first environment whose row qs_set_external_wrench refused, 0 if none */,
        CTL_RENDER_REFUSED = 23 + QS_COHORTS /* 1 + the first position of a qs_render call's env_ids that held an id out of range, 0 if none */,
        CTL_FORK_REFUSED = 24 + QS_COHORTS /* 1 + the first environment whose source qs_fork refused (outside [-1, N)), 0 if none */,
-       CTL_N = 25 + QS_COHORTS };
+       CTL_SOLO_CNT = 25 + QS_COHORTS /* three: fill counts of the solo waves' lists */,
+       CTL_SOLO_PATH = 28 + QS_COHORTS /* QS_DEVCTR_SOLO_PATH */,
+       CTL_N = 29 + QS_COHORTS };
+static_assert(CTL_DEV + QS_DEVCTR_SOLO_PATH == CTL_SOLO_PATH, "the solo waves' counter sits where count_rare_path (qs_lane.h) counts it");
+
+// Risk measure of the solo waves: how far the lowest of this leg's five support candidates (own trunk corner, hip housing, the two ends of
+// the thigh box, knee end of the calf box) is from its contact range, from the state in the record -- the expressions of the substep's
+// vote (qs_core.h: h_trunk, h_hip, h_th_hi, h_th_lo, h_cf_hi against THR_*).  A prediction only: no result depends on it.
+__device__ __forceinline__ float link_clearance(const float* rec) {
+    using namespace qs::go1;
+    const float fx = LaneDev::fx(), sy = LaneDev::sy();
+    const float x = rec[R_QUAT], y = rec[R_QUAT + 1], z = rec[R_QUAT + 2], w = rec[R_QUAT + 3];
+    const float sc = 2.0f / (x * x + y * y + z * z + w * w);
+    const float Rzx = (x * z - w * y) * sc, Rzy = (y * z + w * x) * sc, Rzz = 1.0f - (x * x + y * y) * sc;
+    const float zc = rec[R_POS + 2];
+    const float q1 = LaneDev::ld_leg(rec, R_Q, 3), q2 = LaneDev::ld_leg(rec, R_Q + 1, 3), q3 = LaneDev::ld_leg(rec, R_Q + 2, 3);
+    const float s1 = __sinf(q1), c1 = __cosf(q1), s2 = __sinf(q2), c2 = __cosf(q2), s23 = __sinf(q2 + q3), c23 = __cosf(q2 + q3);   // (fast forms: a prediction)
+    const float p1x = fx * HIP_X, p1y = sy * HIP_Y;
+    const float p2x = p1x, p2y = p1y + c1 * (sy * THIGH_Y), p2z = s1 * (sy * THIGH_Y);
+    const float p3x = p2x + s2 * LEG_Z, p3y = p2y - s1 * c2 * LEG_Z, p3z = p2z + c1 * c2 * LEG_Z;
+    const float az = Rzy * c1 + Rzz * s1;
+    const float gx2 = Rzx * c2 + Rzy * s1 * s2 - Rzz * c1 * s2, gx3 = Rzx * c23 + Rzy * s1 * s23 - Rzz * c1 * s23;
+    const float gp1 = Rzx * p1x + Rzy * p1y, gp2 = Rzx * p2x + Rzy * p2y + Rzz * p2z, gp3 = Rzx * p3x + Rzy * p3y + Rzz * p3z;
+    const float h_trunk = zc + Rzx * (fx * TRUNK_HALF[0]) + Rzy * (sy * TRUNK_HALF[1]) - fabsf(Rzz) * TRUNK_HALF[2];
+    const float h_hip = zc + gp1 - HIP_CYL_HALF_LEN * fabsf(az) - HIP_CYL_R * sqrtf(fmaxf(1.0f - az * az, 0.0f));
+    const float th_off = fabsf(gx2) * THIGH_HALF[0] + fabsf(az) * THIGH_HALF[1], cf_off = (fabsf(gx3) + fabsf(az)) * CALF_HALF[0];
+    const float h_th_hi = zc + gp2 - th_off, h_th_lo = zc + gp3 - th_off, h_cf_hi = zc + gp3 - cf_off;
+    return fminf(fminf(fminf(h_trunk - THR_TRUNK, h_hip - THR_HIP), fminf(h_th_hi, h_th_lo) - THR_THIGH), h_cf_hi - THR_CALF);
+}
 
 // settled-state fields a look-ahead reset copies into the record (everything the 2500-substep settle determines), and the slot's tag.
 // Every load is issued before the first value is used: as four rolled loops (`rec[i] = src[i]`) the copy was a load, a wait and an LDS write
@@ -264,7 +319,7 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
                                                  uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep,
                                                  float* __restrict__ term_obs, LookAhead la,
                                                  unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail,
-                                                 PushTab push) {
+                                                 PushTab push, SoloWaves solo) {
     // the friction model is compiled in (qs_config::friction_cone picks the kernel at launch).  Everything of the full build is inlined in
     // both kernels: as real functions (round 2) the many-rows solvers took State / Out by reference, which kept them in memory around the
     // call, and expressions that then span a store and a load are no longer contracted into the FMAs the common-path build forms -- a wave
@@ -273,28 +328,41 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     using EH = Env<LaneDev, CONE, true, SOFT, RACK>;    // the env step: common-path substeps, then (rare) the full build's (qs_env.h, Env::step)
     // LDS (sized at launch, step_lds_bytes): the 16 records at stride `ls`, the observation rows, the action rows
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-    const qs_config& cfg = *cfgp;
+    // solo waves (SoloWaves): only in the one-wave-per-SIMD kernels without rack or soft payload; F = 0 elsewhere, and all of it folds away
+    const int F = (WAVES == 1 && !SOFT && !RACK) ? solo.F : 0;
+    const bool solo_wave = (int)blockIdx.x < F;                          // wave-uniform
+    const int bid = (int)blockIdx.x - F;                                 // the workgroup's place among the environments' waves and the settle lanes
+    // (a solo wave reads the second copy of the configuration, QsDevCfg::solo = 1: qs_lane.h, count_rare_path)
+    const qs_config& cfg = solo_wave ? reinterpret_cast<const QsDevCfg*>(cfgp)[1].cfg : *cfgp;
     const int ls = (RACK || cfg.payload_soft) ? (int)QS_REC_END : (int)QS_INFO_END;   // = qs::Build::rec_stride (spelled out: see below)
     float* const s_rec = s_dyn;
     float* const s_obs = s_dyn + QS_ENVS_PER_WAVE * ls;
     float* const s_act = s_obs + QS_ENVS_PER_WAVE * QS_MAX_OBS;
     QS_PHASE_BEGIN
     if (tail.rows && blockIdx.x == 0 && threadIdx.x == 0) stats[CTL_TERM_CNT + (tail.parity ^ 1)] = 0ull;
-    const bool settling = (int)blockIdx.x >= lanes.n_env_waves;          // wave-uniform: this workgroup settles staging records
-    const int sw = (int)blockIdx.x - lanes.n_env_waves;                  // settle lanes: which of them
+    if (F > 0 && blockIdx.x == 0 && threadIdx.x == 0) stats[CTL_SOLO_CNT + solo.clr] = 0ull;
+    int solo_env = 0;
+    if (solo_wave) {   // beyond the list's fill count: nobody to step
+        const unsigned long long cnt = stats[CTL_SOLO_CNT + solo.rd];
+        if ((unsigned long long)blockIdx.x >= cnt) return;
+        solo_env = solo.list_rd[blockIdx.x];
+        if ((unsigned)solo_env >= (unsigned)cfg.n_envs) return;          // (never: the list holds what a step of this handle wrote)
+    }
+    const bool settling = bid >= lanes.n_env_waves;                      // wave-uniform: this workgroup settles staging records
+    const int sw = bid - lanes.n_env_waves;                              // settle lanes: which of them
     int cohort = 0;
 #pragma unroll
     for (int c = 1; c < QS_COHORTS; c++) cohort += settling && sw >= lanes.wave0[c] ? 1 : 0;
-    const int first = settling ? cohort * lanes.slice + (sw - lanes.wave0[cohort]) * QS_ENVS_PER_WAVE : (int)blockIdx.x * QS_ENVS_PER_WAVE;
+    const int first = settling ? cohort * lanes.slice + (sw - lanes.wave0[cohort]) * QS_ENVS_PER_WAVE : (solo_wave ? solo_env : bid * QS_ENVS_PER_WAVE);
     // CTL_R[cohort] is only written between launches (k_lookahead_plan)
-    const int limit = settling ? cohort * lanes.slice + (int)stats[CTL_R + cohort] : cfg.n_envs;
+    // (a solo wave: its one environment in slot 0, parked records behind it)
+    const int limit = settling ? cohort * lanes.slice + (int)stats[CTL_R + cohort] : (solo_wave ? first + 1 : cfg.n_envs);
     if (first >= limit) return;
     const int settle_n = settling ? lanes.settle_n[cohort] : 0;
     if (settling && settle_n == 0) return;                               // cohort not started yet
     float* const base = settling ? lanes.staging : recs;
     const int slot = threadIdx.x >> 2;
     const int env = first + slot;
-    const bool valid = env < limit;
     const int d = cfg.action_dim, od = cfg.obs_dim;
     QS_PHASE(26)
     // the quad of an environment fetches its action row (lane l takes entries l, l + 4, l + 8) -- issued before the tile loads, whose
@@ -302,26 +370,32 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     float a_pre[3] = {0.0f, 0.0f, 0.0f};
     float p_rem = 0.0f;                                                  // substeps of a push left at the start of this step (settle lanes: none)
     int2 job = make_int2(0, 0);                                          // settle lanes: whose reset this record is (environment, episode)
+    // home waves: the environment is a solo wave's in this launch (the flag travels with the action row); its quad steps the parked record
+    int moved = 0;
     if (!settling) {
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             const int k = (int)(threadIdx.x & 3u) + 4 * j;
-            if (k < d && valid) a_pre[j] = actions[(size_t)env * d + k];
+            if (k < d && env < limit) a_pre[j] = actions[(size_t)env * d + k];
         }
-        if (push.rows && valid) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
-    } else job = lanes.stage_jobs[valid ? env : first];
+        if (F > 0 && !solo_wave && env < limit) moved = solo.moved_rd[env];
+        if (push.rows && env < limit) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
+    } else job = lanes.stage_jobs[env < limit ? env : first];
     const bool spawn = settling && lanes.spawn[cohort], last = settling && lanes.last[cohort];
     const int load_extent = settling ? (spawn ? 0 : ((RACK || cfg.payload_soft) ? (int)TILE_ALL : (int)QS_SETTLE_END)) : (RACK ? (int)TILE_ALL : tile_extent(cfg, false));
     // (a settle's first slice writes parameters and spawn state itself and reads nothing; its last slice leaves a whole record behind,
     // of which only the settled fields mean anything: the rest is zero rather than whatever the LDS held)
-    if (load_extent > 0) tile_load(s_rec, base, first, limit, load_extent, ls);
+    if (load_extent > 0) tile_load(s_rec, base, first, limit, load_extent, ls, settling ? nullptr : solo.parked);
     if (spawn || last) zero_tile_tail(s_rec, load_extent, ls);
+    const bool valid = env < limit && moved == 0;                        // this quad steps an environment (or a staging record) of its own
+    const unsigned long long not_mine = F > 0 ? __ballot(moved != 0) : 0ull;   // wave-uniform: slots that are a solo wave's
+    if (__builtin_expect(not_mine != 0ull, 0)) tile_park(s_rec, solo.parked, not_mine, load_extent, ls);
     QS_PHASE(27)
-    if (!settling) {
+    if (!settling) {   // (a quad on the parked record holds the pose it was parked in: the settle action)
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             const int k = (int)(threadIdx.x & 3u) + 4 * j;
-            if (k < d) s_act[slot * 12 + k] = a_pre[j];
+            if (k < d) s_act[slot * 12 + k] = valid || solo.parked == nullptr ? a_pre[j] : cfg.settle_action[k];
         }
     }
     QS_PHASE(28)
@@ -334,7 +408,7 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     if (spawn) { E::settle_spawn(cfg, rec, gid, job.y); LaneDev::sync(); }
     const bool any_trace = tap.rows != nullptr && !settling && tap.env >= first && tap.env < first + QS_ENVS_PER_WAVE;   // wave-uniform
     QS_PHASE(13)
-    float* const trow = any_trace && env == tap.env ? tap.rows : nullptr;
+    float* const trow = any_trace && valid && env == tap.env ? tap.rows : nullptr;
     // wave-uniform: some environment of the wave has a push pending; then every quad reads its own row in the substeps (wave-mates without a
     // push select nothing of it, Sim::push_wrench)
     const bool any_push = push.rows != nullptr && __any(p_rem > 0.0f);
@@ -361,6 +435,21 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
         return;
     }
     const bool dn = r.done > 0.5f;
+    const int store_n = solo_wave ? first + 1 : cfg.n_envs;              // tile_store / obs_store: the records behind `first` that are this wave's
+    if (F > 0) {
+        // who steps this environment in the next launch: a solo wave if a link is within `reach` of its contact range and the list has room
+        LaneDev::sync();
+        float clr = link_clearance(rec);
+        clr = fminf(clr, LaneDev::xorl<1>(clr)); clr = fminf(clr, LaneDev::xorl<2>(clr));
+        if (valid && (threadIdx.x & 3) == 0) {
+            int mv = 0;
+            if (clr < solo.reach && !dn) {
+                const unsigned long long ticket = atomicAdd(&stats[CTL_SOLO_CNT + solo.wr], 1ull);
+                if (ticket < (unsigned long long)F) { solo.list_wr[ticket] = env; mv = 1; }
+            }
+            solo.moved_wr[env] = mv;
+        }
+    }
     // the push counts down by the step's substeps; an episode that ended (its auto-reset below, or the caller's reset) cancels it
     if (any_push && valid && p_rem > 0.0f && (threadIdx.x & 3) == 0)
         push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM] = dn ? 0.0f : fmaxf(p_rem - (float)cfg.action_repeat, 0.0f);
@@ -401,8 +490,8 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
                 // k_reset does) and only the resetting environments keep the result -- one whose state was ready gets from its own settle the
                 // very bits it had copied from its slot.
                 __syncthreads();
-                tile_store(s_rec, recs, first, cfg.n_envs, QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls);
-                obs_store(s_obs, min(QS_ENVS_PER_WAVE, cfg.n_envs - first), od, first, obs_out, rew_out == nullptr, obs_keep);
+                tile_store(s_rec, recs, first, store_n, QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls, not_mine);
+                obs_store(s_obs, min(QS_ENVS_PER_WAVE, store_n - first), od, first, obs_out, rew_out == nullptr, obs_keep, not_mine);
                 __syncthreads();
                 E::reset(cfg, rec, ob, gid, true);
                 if (do_reset && !ahead && (threadIdx.x & 3) == 0) atomicAdd(&stats[CTL_SETTLE_SUBSTEPS], (unsigned long long)cfg.settle_steps);
@@ -423,16 +512,16 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
         }
     }
     __syncthreads();
-    tile_store(s_rec, recs, first, cfg.n_envs, any_reset ? 0 : (int)QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls);
-    obs_store(s_obs, min(QS_ENVS_PER_WAVE, cfg.n_envs - first), od, first, obs_out, rew_out == nullptr, obs_keep);
+    tile_store(s_rec, recs, first, store_n, any_reset ? 0 : (int)QS_RW_BEGIN, RACK ? (int)TILE_ALL : tile_extent(cfg, true), ls, not_mine);
+    obs_store(s_obs, min(QS_ENVS_PER_WAVE, store_n - first), od, first, obs_out, rew_out == nullptr, obs_keep, not_mine);
     QS_PHASE(15)
 }
 
 #define QS_STEP_ARGS const qs_config* __restrict__ cfgp, float* __restrict__ recs, const float* __restrict__ actions, float* __restrict__ obs_out,    \
                      float* __restrict__ rew_out, uint8_t* __restrict__ done_out, uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep, \
                      float* __restrict__ term_obs, LookAhead la, unsigned long long* __restrict__ stats, SettleLanes lanes, TraceTap tap, DemoTab demo, TermTail tail, \
-                     PushTab push
-#define QS_STEP_PASS cfgp, recs, actions, obs_out, rew_out, done_out, trunc_out, obs_keep, term_obs, la, stats, lanes, tap, demo, tail, push
+                     PushTab push, SoloWaves solo
+#define QS_STEP_PASS cfgp, recs, actions, obs_out, rew_out, done_out, trunc_out, obs_keep, term_obs, la, stats, lanes, tap, demo, tail, push, solo
 // One wave per SIMD: the whole 512-entry register file (256 VGPR + 256 AGPR) for one wave.  The common-path substep loop holds no scratch
 // instruction (tools/isa_headline.py); the cold code behind it -- the full build's substeps of a handed-over step, the in-step settle --
 // spills (~110 values, ~470 B of scratch per lane).  The launch time is one wave's instruction stream, so this is the variant while the
@@ -628,6 +717,19 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_f
 template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_fill_rack(const qs_config* __restrict__ cfgp, LookAhead la) { QS_RESET_LDS lookahead_fill_body<CONE, true>(cfgp, la, s_rec, s_obs); }
 #undef QS_RESET_LDS
 
+// The parked record of a handle (qs_create): environment 0's settled state of episode 0 out of its look-ahead slot -- a whole record as a
+// reset leaves it, filter history and last action at the settle action -- lifted 5 m, at rest.  A quad that steps it under the settle
+// action touches nothing and reaches no joint stop within an env step, so it never asks for a rare path; it is loaded fresh by every
+// launch and never stored.
+__global__ void k_make_parked(const float* __restrict__ slot, float* __restrict__ parked) {
+    for (int i = threadIdx.x; i < QS_REC; i += blockDim.x) {
+        float v = i < QS_REC_END ? slot[i] : 0.0f;
+        if (i == R_POS + 2) v += 5.0f;
+        if ((i >= R_VLIN && i < R_VLIN + 3) || (i >= R_VANG && i < R_VANG + 3) || (i >= R_QD && i < R_QD + 12) || (i >= R_WARM && i < R_WARM + 4)) v = 0.0f;
+        parked[i] = v;
+    }
+}
+
 __global__ void k_gather(const float* __restrict__ recs, int n, int off, int dim, float* __restrict__ out, int as_int) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * dim) return;
@@ -711,6 +813,10 @@ struct qs_handle {
     int push_live;          // a push may be pending: the step launches read d_push (cleared by a reset of every environment)
     int n_simd, step_variant;   // SIMDs of the device; 0 = pick k_step / k_step_dense by grid size, 1 / 2 = forced (QS_STEP_VARIANT)
     unsigned long long* d_stats;
+    // solo waves (SoloWaves): the parked record, the flags [2][N], the lists [3][QS_SOLO_MAX]; solo_f = workgroups asked for (qs_solo_waves),
+    // solo_live = what the last launch carried (a change starts from clean flags), solo_tick = launches since then
+    float* d_parked; int* d_moved; int* d_solo_list;
+    int solo_f, solo_live; float solo_reach; long long solo_tick;
     TermTail tail;          // set for the launch of a host-path step
     struct HostPath* host;  // qs_host_step_*: pinned buffers and the device result block (allocated at first use)
     hipEvent_t ev0, ev1;
@@ -810,7 +916,7 @@ static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs
         h->step_variant = v ? atoi(v) : 0;
     }
     const size_t n = (size_t)cfg->n_envs;
-    QS_HIP(hipMalloc(&h->d_cfg, sizeof(QsDevCfg)));   // the configuration, and behind it the address of the rare paths' counters (qs_lane.h)
+    QS_HIP(hipMalloc(&h->d_cfg, 2 * sizeof(QsDevCfg)));   // the configuration, and behind it the address of the rare paths' counters (qs_lane.h); twice: the second copy is the solo waves'
     QS_HIP(hipMalloc(&h->d_rec, n * QS_REC * sizeof(float)));
     QS_HIP(hipMalloc(&h->d_obs, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMalloc(&h->d_term_obs, n * cfg->obs_dim * sizeof(float)));
@@ -823,6 +929,8 @@ static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs
         for (int i = 0; i < 3; i++) dc.rack_pos[i] = h->rack.anchor_pos[i];
         for (int i = 0; i < 4; i++) dc.rack_quat[i] = h->rack.anchor_quat[i];
         QS_HIP(hipMemcpy(h->d_cfg, &dc, sizeof(dc), hipMemcpyHostToDevice));
+        dc.solo = 1;
+        QS_HIP(hipMemcpy(reinterpret_cast<QsDevCfg*>(h->d_cfg) + 1, &dc, sizeof(dc), hipMemcpyHostToDevice));
     }
     QS_HIP(hipMemset(h->d_obs, 0, n * cfg->obs_dim * sizeof(float)));
     QS_HIP(hipMemset(h->d_term_obs, 0, n * cfg->obs_dim * sizeof(float)));
@@ -862,6 +970,20 @@ static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs
         });
         QS_HIP(hipGetLastError());
         h->lanes_on = 1;
+        // solo waves: the parked record, flags and lists
+        QS_HIP(hipMalloc(&h->d_parked, QS_REC * sizeof(float)));
+        QS_HIP(hipMalloc(&h->d_moved, 2 * n * sizeof(int)));
+        QS_HIP(hipMalloc(&h->d_solo_list, 3 * QS_SOLO_MAX * sizeof(int)));
+        QS_HIP(hipMemsetAsync(h->d_moved, 0, 2 * n * sizeof(int), h->stream));
+        QS_HIP(hipMemsetAsync(h->d_solo_list, 0, 3 * QS_SOLO_MAX * sizeof(int), h->stream));
+        hipLaunchKernelGGL(k_make_parked, dim3(1), dim3(256), 0, h->stream, h->la.slots, h->d_parked);
+        QS_HIP(hipGetLastError());
+        const char* sv = getenv("QS_SOLO_WAVES");
+        const char* rv = getenv("QS_SOLO_REACH");
+        h->solo_f = sv ? atoi(sv) : QS_SOLO_DEFAULT;
+        if (h->solo_f < 0) h->solo_f = 0;
+        if (h->solo_f > QS_SOLO_MAX) h->solo_f = QS_SOLO_MAX;
+        h->solo_reach = rv ? (float)atof(rv) : QS_SOLO_REACH_DEFAULT;
     }
     QS_HIP(hipStreamSynchronize(h->stream));
     return 0;
@@ -881,6 +1003,9 @@ void qs_destroy(qs_handle* h) {   // also used on a partially built handle (null
     if (h->d_demo) hipFree(h->d_demo);
     if (h->d_push) hipFree(h->d_push);
     if (h->d_fork) hipFree(h->d_fork);
+    if (h->d_parked) hipFree(h->d_parked);
+    if (h->d_moved) hipFree(h->d_moved);
+    if (h->d_solo_list) hipFree(h->d_solo_list);
     host_path_free(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -956,6 +1081,15 @@ int qs_settle_lanes(qs_handle* h, int on) {
     return 0;
 }
 
+int qs_solo_waves(qs_handle* h, int f, float reach) {
+    if (!h) QS_FAIL(-1, "null handle");
+    if (f < -1 || f > QS_SOLO_MAX) QS_FAIL(-1, "qs_solo_waves: between 0 (off) and %d solo waves per launch (-1: as it is), got %d", QS_SOLO_MAX, f);
+    if (f > 0 && !h->d_parked) QS_FAIL(-1, "solo waves need the look-ahead reset states (cfg.reset_lookahead > 0, not QS_RAND_KEEP): the parked record is made from one");
+    if (f >= 0) h->solo_f = f;
+    if (reach > 0.0f) h->solo_reach = reach;
+    return 0;
+}
+
 static int launch_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc);
 
 int qs_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
@@ -981,7 +1115,39 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     PushTab push; push.rows = h->push_live ? h->d_push : nullptr;
     int grid = lanes.n_env_waves;
     bool lanes_fit = true;      // the environments' waves and the lanes' usual share fit the SIMDs
-    if (h->la.K > 0 && h->lanes_on) {
+    const bool with_lanes = h->la.K > 0 && h->lanes_on;
+    // the settle lanes' usual share per cohort next to `extra` more workgroups, and whether all of it fits the SIMDs in one round
+    auto lanes_share = [&](int extra, bool* fit) {
+        const int free_simd = h->n_simd - lanes.n_env_waves - extra;
+        int base_waves = h->slice / QS_ENVS_PER_WAVE;
+        if (h->step_variant != 2 && free_simd / QS_COHORTS >= 64 && base_waves > free_simd / QS_COHORTS) base_waves = free_simd / QS_COHORTS;
+        *fit = lanes.n_env_waves + extra + (with_lanes ? QS_COHORTS * base_waves : 0) <= h->n_simd;
+        return base_waves;
+    };
+    // Solo waves: the one-wave-per-SIMD kernels without rack or soft payload, with the links' response on (without it nothing lands on the
+    // many-rows path for long), and only while they fit next to everything else in one round (they count against the SIMD budget).
+    int F = 0;
+    if (h->solo_f > 0 && h->d_parked && h->cfg.body_contacts && !h->cfg.payload_soft && !h->rack.on && h->step_variant != 2) {
+        bool fit = false;
+        lanes_share(h->solo_f, &fit);
+        if (fit) F = h->solo_f;
+    }
+    if (F != h->solo_live) {   // switched on, off or resized: every environment is its home wave's again
+        if (h->d_moved) QS_HIP(hipMemsetAsync(h->d_moved, 0, 2 * (size_t)h->cfg.n_envs * sizeof(int), h->stream));
+        QS_HIP(hipMemsetAsync(h->d_stats + CTL_SOLO_CNT, 0, 3 * sizeof(unsigned long long), h->stream));
+        h->solo_live = F; h->solo_tick = 0;
+    }
+    SoloWaves solo;
+    memset(&solo, 0, sizeof(solo));
+    solo.parked = h->d_parked;
+    if (F > 0) {
+        const long long i = h->solo_tick++;
+        solo.F = F; solo.rd = (int)(i % 3); solo.wr = (int)((i + 1) % 3); solo.clr = (int)((i + 2) % 3); solo.reach = h->solo_reach;
+        solo.moved_rd = h->d_moved + (size_t)(i & 1) * h->cfg.n_envs; solo.moved_wr = h->d_moved + (size_t)((i + 1) & 1) * h->cfg.n_envs;
+        solo.list_rd = h->d_solo_list + solo.rd * QS_SOLO_MAX; solo.list_wr = h->d_solo_list + solo.wr * QS_SOLO_MAX;
+        grid += F;
+    }
+    if (with_lanes) {
         // one settle = settle_steps substeps = `epoch` launches of action_repeat substeps (the last one takes the remainder);
         // cohort c runs the same schedule c * epoch / QS_COHORTS launches later
         const int rep = h->cfg.action_repeat, epoch = (h->cfg.settle_steps + rep - 1) / rep;
@@ -991,11 +1157,8 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
         // N = 8192 cost the launch 0.4 %); how many of them work is decided on the device (k_lookahead_plan): normally what fits the SIMDs
         // the environments leave idle (base_waves per cohort: the one-wave-per-SIMD kernel then runs the launch in one round), more
         // when environments run short of states.
-        const int free_simd = h->n_simd - lanes.n_env_waves;
         const int cohort_waves = slice / QS_ENVS_PER_WAVE;
-        int base_waves = cohort_waves;
-        if (h->step_variant != 2 && free_simd / QS_COHORTS >= 64 && base_waves > free_simd / QS_COHORTS) base_waves = free_simd / QS_COHORTS;
-        lanes_fit = n_waves(h->cfg.n_envs) + QS_COHORTS * base_waves <= h->n_simd;
+        const int base_waves = lanes_share(F, &lanes_fit);
         for (int c = 0; c < QS_COHORTS; c++) {
             const long long t = h->tick - (long long)c * epoch / QS_COHORTS;
             lanes.wave0[c] = c * cohort_waves;
@@ -1021,7 +1184,7 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     const qs::Build build = handle_build(h);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(QS_WAVE), build.step_lds_bytes(), h->stream, h->d_cfg, h->d_rec, actions, obs, rew, done, trunc,
-                           h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push);
+                           h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push, solo);
     };
     qs::with_build(build, [&](auto cone, auto soft, auto rack) {
         if constexpr (rack()) launch(dense ? k_step_dense_rack<cone()> : k_step_rack<cone()>);
@@ -1358,6 +1521,7 @@ int qs_counter(qs_handle* h, int which, uint64_t* value) {
         break;
     case QS_COUNTER_LIMIT_PATH_SUBSTEPS: QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_DEV + QS_DEVCTR_RARE_PATH], sizeof(v), hipMemcpyDeviceToHost)); break;
     case QS_COUNTER_SELF_NARROW_SUBSTEPS: QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_DEV + QS_DEVCTR_SELF_NARROW], sizeof(v), hipMemcpyDeviceToHost)); break;
+    case QS_COUNTER_SOLO_PATH_SUBSTEPS: QS_HIP(hipMemcpy(&v, &h->d_stats[CTL_SOLO_PATH], sizeof(v), hipMemcpyDeviceToHost)); break;
     default: QS_FAIL(-1, "unknown counter %d", which);
     }
     *value = v;

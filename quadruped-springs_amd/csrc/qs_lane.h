@@ -87,9 +87,11 @@ QS_FN float qflag(bool m) { return m ? 1.0f : 0.0f; }
 // The configuration as the kernels see it: the public struct, and behind it the handle's counter block -- telemetry of the rare paths
 // (per HANDLE since round 4; a process-wide pair of __device__ variables before: two handles on one GPU mixed their counts) -- and the rack's
 // anchor (qs_rack: read by the RACK builds only, qs_core.h; the host emulation passes the same struct)
-struct QsDevCfg { qs_config cfg; unsigned long long* counters; float rack_pos[3]; float rack_quat[4]; };
+// (`solo`: the copy of the configuration that the step kernel's solo waves read -- a robot about to fall, alone in its wave -- so that
+// their many-rows substeps are counted on their own as well)
+struct QsDevCfg { qs_config cfg; unsigned long long* counters; float rack_pos[3]; float rack_quat[4]; int solo; };
 #if defined(__HIPCC__)
-enum { QS_DEVCTR_RARE_PATH = 0, QS_DEVCTR_SELF_NARROW = 1 };   // wave-substeps through the many-rows solve / whose broad phase asked for the link-link tests
+enum { QS_DEVCTR_RARE_PATH = 0, QS_DEVCTR_SELF_NARROW = 1, QS_DEVCTR_SOLO_PATH = 18 /* of RARE_PATH: those of solo waves */ };   // wave-substeps through the many-rows solve / whose broad phase asked for the link-link tests
 struct LaneDev {
     using V = float;
     using M = bool;
@@ -156,7 +158,13 @@ struct LaneDev {
     // the wave's sixteen observation rows (LDS) from the row of this lane's environment
     static QS_DEV float* wave_scratch(float* row) { return row - (size_t)(threadIdx.x >> 2) * QS_MAX_OBS; }
     // (every qs_config the device code gets is the first member of a QsDevCfg in device memory: qs_hip.hip, create_impl)
-    static QS_DEV void count_rare_path(const qs_config& cfg) { if (threadIdx.x == 0) atomicAdd(&reinterpret_cast<const QsDevCfg&>(cfg).counters[QS_DEVCTR_RARE_PATH], 1ull); }
+    static QS_DEV void count_rare_path(const qs_config& cfg) {
+        if (threadIdx.x == 0) {
+            const QsDevCfg& dc = reinterpret_cast<const QsDevCfg&>(cfg);
+            atomicAdd(&dc.counters[QS_DEVCTR_RARE_PATH], 1ull);
+            if (dc.solo) atomicAdd(&dc.counters[QS_DEVCTR_SOLO_PATH], 1ull);
+        }
+    }
     static QS_DEV void count_self_narrow(const qs_config& cfg) { if (threadIdx.x == 0) atomicAdd(&reinterpret_cast<const QsDevCfg&>(cfg).counters[QS_DEVCTR_SELF_NARROW], 1ull); }
     // orders LDS traffic between the lanes of a wave (in-order LDS queue per wave; this only pins the compiler)
     static QS_DEV void sync() {

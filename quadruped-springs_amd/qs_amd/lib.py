@@ -15,7 +15,7 @@ ABI_LIBRARY = 9   # QS_ABI_VERSION of include/qs_amd.h this file was written aga
 EXPORTS = (
     "qs_create", "qs_destroy", "qs_set_stream", "qs_reset", "qs_reset_to", "qs_get_obs", "qs_step", "qs_step_fused", "qs_get_state", "qs_set_state",
     "qs_info_dim", "qs_get_info", "qs_set_params", "qs_stats", "qs_enable_timing", "qs_last_step_kernel_ms",
-    "qs_settle_lanes", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_create_ex", "qs_set_rack", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
+    "qs_settle_lanes", "qs_solo_waves", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_create_ex", "qs_set_rack", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
     "qs_norm_create", "qs_norm_destroy", "qs_norm_dims", "qs_norm_set_stream", "qs_norm_set_stats", "qs_norm_get_stats", "qs_norm_reset", "qs_norm_step",
     "qs_norm_step_io", "qs_host_set_norm",
     "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
@@ -115,6 +115,8 @@ def load():
     if hasattr(lib, "qs_render"):   # (ABI 7)
         lib.qs_render.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp]
         lib.qs_render_states.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp, vp]
+    if hasattr(lib, "qs_solo_waves"):   # (added under ABI 9; an older library under QS_LIB_PATH lacks it)
+        lib.qs_solo_waves.argtypes = [vp, i32, C.c_float]
     lib.qs_counter.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
     lib.qs_counters_async.argtypes = [vp, vp]
     f32, f64, pd = C.c_float, C.c_double, C.POINTER(C.c_double)

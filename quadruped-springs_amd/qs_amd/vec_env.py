@@ -21,7 +21,7 @@ FRAME = dict(link=1, world=2)   # QS_FRAME_LINK / QS_FRAME_WORLD = pybullet.LINK
 
 
 class QuadrupedVecEnv(SB3VecEnv):
-    def __init__(self, num_envs=1, device=0, auto_reset=True, reset_lookahead=None, copy_outputs=True, **env_kwargs):
+    def __init__(self, num_envs=1, device=0, auto_reset=True, reset_lookahead=None, copy_outputs=True, solo_waves=None, solo_reach=None, **env_kwargs):
         """reset_lookahead = K: every environment keeps the settled reset states of its next K episodes ready (computed by extra workgroups
         of the step kernel while the environments step), so a reset is a copy; results are bitwise those of K = 0, where every reset runs
         the reference's 2500-substep settle in place (gym_env.py:278-297, 323-329).  Default: 16 with auto_reset, 0 without.  What K = 16
@@ -30,10 +30,13 @@ class QuadrupedVecEnv(SB3VecEnv):
         lanes' workgroups of five full cohorts, of which those beyond the cohort's jobs leave at once (5120 of them at N = 8192: 0.4 % of the
         launch; 40960 next to 4096 working ones at N = 65536: under 1 %).  A handle whose episodes never end early can do with K = 2.
         copy_outputs=False: step() / step_wait() return views of the page-locked result block instead of copies (valid until the end of
-        the next step: two blocks alternate)."""
+        the next step: two blocks alternate).
+        solo_waves = F / solo_reach = metres: see solo_waves() (None: the library's defaults)."""
         cfg, meta = build_config(n_envs=num_envs, auto_reset=auto_reset, **env_kwargs)
         cfg.reset_lookahead = int((16 if auto_reset else 0) if reset_lookahead is None else reset_lookahead)
         self._setup(cfg, meta, device, copy_outputs)
+        if solo_waves is not None or solo_reach is not None:
+            self.solo_waves(solo_waves, solo_reach)
 
     @classmethod
     def from_config(cls, cfg, meta, device=0, copy_outputs=True, load_demo=True):
@@ -434,7 +437,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         return dict(settle_substeps=a.value, resets=b.value)
 
     COUNTERS = dict(settle_substeps=0, resets=1, lookahead_served=2, lookahead_settled=3, limit_path_substeps=4, self_narrow_substeps=5,
-                    reset_stalls=6, lookahead_backlog=7)
+                    reset_stalls=6, lookahead_backlog=7, solo_path_substeps=8)
 
     def counter(self, which):
         v = C.c_uint64(0)
@@ -448,6 +451,17 @@ class QuadrupedVecEnv(SB3VecEnv):
         self._stream()
         _lib.check(self.lib.qs_counters_async(self.h, self._ptr(out)))
         return out
+
+    def solo_waves(self, f=None, reach=None):
+        """Solo waves (qs_solo_waves): up to `f` robots per launch that are about to put a link on the floor -- one within `reach` metres of
+        its contact range at the end of the previous step -- step in a workgroup of their own instead of holding up their fifteen
+        wave-mates.  f = 0: off; None: keep (the library starts with 128, or QS_SOLO_WAVES).  Results do not change, only the launch time.
+        counter("solo_path_substeps") / counter("limit_path_substeps") is the share of the many-rows wave-substeps they take."""
+        if not hasattr(self.lib, "qs_solo_waves"):
+            raise RuntimeError("this libqs_hip.so has no qs_solo_waves: rebuild it (python quadruped-springs_amd/build.py --force)")
+        if f is None:   # keep the count: an unchanged F needs the current one, which only the library knows -- so reach alone goes through F = -1
+            f = -1
+        _lib.check(self.lib.qs_solo_waves(self.h, int(f), float(reach if reach is not None else 0.0)))
 
     def enable_timing(self, on=True):
         """True / False: arm / disarm the batch timing of the step kernel; 2: close the batch now (the closing event goes onto the stream,
