@@ -504,6 +504,40 @@ int qs_ppo_adam(qs_ppo* h, const float* grad, const qs_ppo_hyper* hyper, int ste
 /* samples refused since the last call (waits for the handle's stream) */
 int qs_ppo_refusals(qs_ppo* h, unsigned long long* out);
 
+/* ---- ARS's bookkeeping on the device (sb3_contrib 1.5 as remembered: ARS.evaluate_candidates' episode accounting and ARS._do_one_update; the
+ * package was not available to check against).  The arithmetic, its roundings and its summation order are csrc/qs_ars.h.  n_envs = P m
+ * environments for P = 2 n_delta candidates; candidate p owns the environments [p m, (p + 1) m), as a qs_policy with n_policies = P does; the
+ * + candidates come first.  The handle owns the per-environment accounts (return, length, episodes, alive), two counters (environments
+ * alive, steps summed) and the results of the last finish.  Every call but qs_ars_alive is stream-ordered, waits for nothing and allocates
+ * nothing; there are no floating-point atomics, so the same inputs give the same bits. */
+typedef struct qs_ars qs_ars;
+/* Refuses, with text in qs_last_error(): n_delta outside [1, 1024], n_envs that is no positive multiple of 2 n_delta, n_params < 1,
+ * episodes_per_env < 1. */
+int qs_ars_create(int n_envs, int n_delta, int n_params, int episodes_per_env, int device, qs_ars** out);
+void qs_ars_destroy(qs_ars* h);
+int qs_ars_set_stream(qs_ars* h, void* hip_stream);
+/* candidates [2 n_delta][n_params] (what qs_policy_set_params was given) = theta [n_params] +- sigma * delta [n_delta][n_params] */
+int qs_ars_perturb(qs_ars* h, const float* theta, const float* delta, float sigma, float* candidates);
+/* the start of a rollout: every account zero, every environment alive */
+int qs_ars_begin(qs_ars* h);
+/* One environment step: raw_reward [n_envs] float32 (before any normalisation), done [n_envs] uint8.  An alive environment adds the reward and
+ * one step; where done it counts an episode and dies at episodes_per_env of them.  A dead environment changes nothing. */
+int qs_ars_account(qs_ars* h, const float* raw_reward, const uint8_t* done);
+/* the number of environments alive, copied to the host (WAITS for the handle's stream) */
+int qs_ars_alive(qs_ars* h, int* out);
+/* the candidates' returns R_p = sum over the block of (return + alive_bonus_offset * length), and the sum of all lengths */
+int qs_ars_returns(qs_ars* h, float alive_bonus_offset);
+/* qs_ars_returns, then ARS._do_one_update: the n_top directions with the largest max(R+, R-) (ties: the lower index first, this project's
+ * rule), step = learning_rate / (n_top * std of their 2 n_top returns + 1e-6), theta += step * sum (R+ - R-) delta, in place.  delta is the
+ * array qs_ars_perturb was given.  Refuses n_top outside [1, n_delta]. */
+int qs_ars_finish(qs_ars* h, float* theta, const float* delta, int n_top, float learning_rate, float alive_bonus_offset);
+/* Getters: a stream-ordered copy into DEVICE memory.  RET float32 [n_envs], LEN and EPISODES int32 [n_envs], ALIVE uint8 [n_envs], N_ALIVE
+ * int32 [1], STEPS uint64 [1] (of the last returns / finish), RETURNS float32 [2 n_delta], IDX int32 [n_delta] and W float32 [n_delta] (the
+ * first n_top entries are the last finish's), STATS float32 [2] = std, step. */
+enum { QS_ARS_GET_RET = 0, QS_ARS_GET_LEN = 1, QS_ARS_GET_EPISODES = 2, QS_ARS_GET_ALIVE = 3, QS_ARS_GET_N_ALIVE = 4, QS_ARS_GET_STEPS = 5,
+       QS_ARS_GET_RETURNS = 6, QS_ARS_GET_IDX = 7, QS_ARS_GET_W = 8, QS_ARS_GET_STATS = 9 };
+int qs_ars_get(qs_ars* h, int what, void* dev_out);
+
 /* ---- Device snapshots: save, restore and fork environments (what pybullet.saveState / restoreState are to the reference's simulator; the CPU
  * oracle's qso_snapshot / qso_restore).  A snapshot is one row of qs_snapshot_info::row_floats floats per environment, in DEVICE memory owned by
  * the caller (16-byte aligned): [the environment's whole record | its push row | its last observation | its terminal observation], layout in
@@ -554,7 +588,7 @@ const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way, and so were the qs_ars_* entries, ARS's bookkeeping.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 9
 int qs_abi_version(void);
 

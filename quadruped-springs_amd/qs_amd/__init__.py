@@ -20,6 +20,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch / a GP
     if name in ("DeviceActorCritic", "DeviceRolloutBuffer", "DevicePPO", "ppo_loss"):
         from . import ppo
         return getattr(ppo, name)
+    if name == "DeviceARS":
+        from .ars import DeviceARS
+        return DeviceARS
     if name == "EnvSnapshot":
         from .snapshot import EnvSnapshot
         return EnvSnapshot

@@ -22,6 +22,8 @@ EXPORTS = (
     "qs_ac_create", "qs_ac_destroy", "qs_ac_set_stream", "qs_ac_set_params", "qs_ac_collect", "qs_ac_values", "qs_ac_bootstrap", "qs_gae",
     "qs_snapshot_info", "qs_snapshot", "qs_restore", "qs_fork", "qs_norm_get_returns", "qs_norm_set_returns",
     "qs_ppo_create", "qs_ppo_destroy", "qs_ppo_set_stream", "qs_ppo_bind", "qs_ppo_grad", "qs_ppo_adam", "qs_ppo_refusals",
+    "qs_ars_create", "qs_ars_destroy", "qs_ars_set_stream", "qs_ars_perturb", "qs_ars_begin", "qs_ars_account", "qs_ars_alive", "qs_ars_returns",
+    "qs_ars_finish", "qs_ars_get",
 )
 
 
@@ -166,6 +168,18 @@ def load():
         lib.qs_ppo_grad.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, vp, i32, C.POINTER(QsPpoHyper), vp, vp]
         lib.qs_ppo_adam.argtypes = [vp, vp, C.POINTER(QsPpoHyper), i32, vp]
         lib.qs_ppo_refusals.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "qs_ars_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
+        lib.qs_ars_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+        lib.qs_ars_destroy.argtypes = [vp]
+        lib.qs_ars_destroy.restype = None
+        lib.qs_ars_set_stream.argtypes = [vp, vp]
+        lib.qs_ars_perturb.argtypes = [vp, vp, vp, f32, vp]
+        lib.qs_ars_begin.argtypes = [vp]
+        lib.qs_ars_account.argtypes = [vp, vp, vp]
+        lib.qs_ars_alive.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.qs_ars_returns.argtypes = [vp, f32]
+        lib.qs_ars_finish.argtypes = [vp, vp, vp, i32, f32, f32]
+        lib.qs_ars_get.argtypes = [vp, i32, vp]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)
