@@ -6,7 +6,10 @@ the candidates, the episode accounting (one small launch per step, the host look
 --host-loop runs the loop this example had before DeviceARS (torch accumulation, a host wait per step, torch's argsort / std / matmul), for
 comparison; tools/time_ars.py times the two against each other.
 
-    python examples/ars.py [--iterations 12] [--n-delta 64] [--episodes 64] [--horizon 300] [--host-loop]"""
+--freeze-done: environments whose episode has ended are no longer stepped (DeviceARS(freeze_done=True), step_tensor(active=)); under this
+example's DeviceVecNormalize(training=True) the statistics then see living robots only, so the numbers printed differ from a run without it.
+
+    python examples/ars.py [--iterations 12] [--n-delta 64] [--episodes 64] [--horizon 300] [--host-loop] [--freeze-done]"""
 import argparse
 import os
 import sys
@@ -60,7 +63,10 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.05)       # sb3_contrib: delta_std
     ap.add_argument("--step-size", type=float, default=0.02)   # sb3_contrib: learning_rate
     ap.add_argument("--host-loop", action="store_true", help="the torch bookkeeping with a host wait per step, as before DeviceARS")
+    ap.add_argument("--freeze-done", action="store_true", help="stop stepping an environment once its episode has ended")
     args = ap.parse_args()
+    if args.host_loop and args.freeze_done:
+        ap.error("--freeze-done belongs to DeviceARS, not to --host-loop")
     env, policy = make(args.n_delta, args.episodes)
     if args.host_loop:
         torch.manual_seed(0)
@@ -72,7 +78,8 @@ def main():
     else:
         # (a candidate's return is the SUM over its block: the step's scale is 1 / (n_top std) of those sums, so the learning rate that
         # matches the host loop's block means is step_size itself -- the update is invariant to a common factor of the returns)
-        ars = DeviceARS(env, policy, n_delta=args.n_delta, n_top=args.n_top, learning_rate=args.step_size, delta_std=args.sigma, horizon=args.horizon, seed=0)
+        ars = DeviceARS(env, policy, n_delta=args.n_delta, n_top=args.n_top, learning_rate=args.step_size, delta_std=args.sigma, horizon=args.horizon, seed=0,
+                        freeze_done=args.freeze_done)
         for it in range(args.iterations):
             per_policy = ars.train_iteration() / args.episodes
             print(f"iteration {it:2d}: mean return {per_policy.mean().item():8.3f}   best candidate {per_policy.max().item():8.3f}")

@@ -6,8 +6,10 @@ they were (a masked restore of a masked snapshot); then the first action of each
 takes, and the rest of that sequence is the next plan.  Prints the real robots' mean return (the rewards of their first episode, plus the task's end-of-episode reward for
 the state they are in if it has not ended: get_info("reward_end")) against the same loop with C = 1 (no
 sampling: the plan is never improved).  Nothing leaves the GPU inside a control step.
+--freeze-done: a candidate whose episode has ended is not rolled out to the horizon (step_tensor(active=)); the scores ignore it from
+there on anyway, so the result printed is the same.
 
-    python examples/mpc.py [--robots 64] [--candidates 63] [--horizon 12] [--steps 150] [--sigma 0.5]"""
+    python examples/mpc.py [--robots 64] [--candidates 63] [--horizon 12] [--steps 150] [--sigma 0.5] [--freeze-done]"""
 import argparse
 import os
 import sys
@@ -20,7 +22,7 @@ import torch
 from qs_amd import QuadrupedVecEnv
 
 
-def run(M, C, H, steps, sigma, seed):
+def run(M, C, H, steps, sigma, seed, freeze_done=False):
     n = M * (1 + C)
     env = QuadrupedVecEnv(num_envs=n, device=0, auto_reset=True, task_env="JUMPING_IN_PLACE", observation_space_mode="PPO_BASIC",
                           action_space_mode="SYMMETRIC", motor_control_mode="PD", enable_springs=True, enable_action_filter=True,
@@ -38,6 +40,7 @@ def run(M, C, H, steps, sigma, seed):
     actions = torch.zeros((n, d), device=dev)
     ret = torch.zeros(M, device=dev)
     alive = torch.ones(M, dtype=torch.bool, device=dev)
+    active = torch.ones(n, dtype=torch.bool, device=dev)           # --freeze-done: the real robots, and the candidates still in their episode
     for _ in range(steps):
         env.fork(src_of=src_of)
         env.snapshot(indices=real_mask, out=keep)
@@ -48,7 +51,11 @@ def run(M, C, H, steps, sigma, seed):
         running = torch.ones(M * C, dtype=torch.bool, device=dev)
         for h in range(H):
             actions[M:] = seq[:, h]
-            _, rew, done, _ = env.step_tensor(actions)
+            if freeze_done:
+                active[M:] = running
+                _, rew, done, _ = env.step_tensor(actions, active=active)
+            else:
+                _, rew, done, _ = env.step_tensor(actions)
             score += rew[M:] * running
             running &= ~done[M:].bool()
         # the task pays at the end of the episode: a candidate still in its episode at the horizon is worth what the task would pay there
@@ -75,9 +82,10 @@ def main():
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--sigma", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--freeze-done", action="store_true", help="stop rolling out a candidate once its episode has ended")
     a = ap.parse_args()
     for C in (a.candidates, 1):
-        r, up = run(a.robots, C, a.horizon, a.steps, a.sigma, a.seed)
+        r, up = run(a.robots, C, a.horizon, a.steps, a.sigma, a.seed, a.freeze_done)
         print(f"C = {C:3d} candidates x H = {a.horizon}: mean return of the {a.robots} real robots over their first episode (at most {a.steps} steps) "
               f"{r:8.3f}, {up} of them still in it")
 

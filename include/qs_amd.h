@@ -242,6 +242,18 @@ int qs_stats(qs_handle* h, uint64_t* settle_substeps, uint64_t* resets);
  * buffer a sharded run all-gathers to the learner rank (one collective per step, qs_amd/sharded.py), written by the step
  * kernel itself instead of being packed from four arrays afterwards. */
 int qs_step_fused(qs_handle* h, const float* actions, float* fused);
+/* qs_step with a per-environment pause.  active [N] uint8, device memory; NULL makes it qs_step.  An environment with active[e] == 0 is
+ * FROZEN for this launch: nobody steps it.  Unchanged: its record (every field, the info block and warm start included), its last
+ * observation, its pending push (no countdown), its look-ahead window, the handle's counters, the trace tap's rows if it is the tapped
+ * environment.  Written for it: obs[e] = its last observation, rew[e] = 0, done[e] = 0, truncated[e] = 0.  It is not reset, gets no
+ * terminal observation and is not counted as a reset.  Every active environment's results are bit for bit those of qs_step.
+ * A wave (16 consecutive environments) without an active one leaves after reading the mask; in a wave with work, a frozen environment's
+ * quad steps the handle's parked record -- a robot hanging in the air that asks for no rare path -- and stores nothing, so a robot on the
+ * floor that is frozen holds up nobody.  With solo waves, a frozen environment is its home wave's again in the next launch.
+ * Handles without a parked record (cfg.reset_lookahead = 0, QS_RAND_KEEP) step a private copy of the frozen environment's own record
+ * instead and store nothing: correct, not faster (and the rare paths' counters still count it).  Refused with payload_soft (the parked
+ * record does not carry the payload block along).  qs_step_fused and qs_host_step_* take no mask. */
+int qs_step_masked(qs_handle* h, const float* actions, const uint8_t* active /*[N] or NULL*/, float* obs, float* rew, uint8_t* done, uint8_t* truncated);
 /* ---- Host (numpy) path: the SB3 consumer of load_model.py:113-133 hands over HOST arrays.  qs_host_step_begin = VecEnv.step_async:
  * `actions` is a host array [N, action_dim] (any memory; copied into page-locked staging before the call returns); the step is enqueued on
  * the handle's stream with its action and result pointers IN that page-locked host memory, mapped into the device's address space: the
@@ -340,6 +352,13 @@ int qs_norm_reset(qs_norm* h, float* obs /* [N,o] */, int training, int norm_obs
  * (get_original_obs / get_original_reward), written by the same pass */
 int qs_norm_step(qs_norm* h, float* obs /* [N,o] */, float* rew /* [N] */, const uint8_t* done /* [N] */, float* term_obs /* [N,o] or NULL */,
                  int training, int norm_obs, int norm_reward, float* raw_obs, float* raw_rew);
+/* qs_norm_step after a qs_step_masked.  active [N] uint8, device memory; NULL makes it qs_norm_step.  When training, the batch moments of
+ * observations and of returns are taken over the rows with active[i] != 0 only, the batch count is their number (summed on the device),
+ * and only those rows' returns advance (returns <- returns*gamma + rew) and go to zero at done; a step without an active row leaves the
+ * statistics as they are.  Every row, frozen ones included, is normalised with the step's statistics, and raw_obs / raw_rew receive every
+ * row.  A mask of ones gives the bits of qs_norm_step. */
+int qs_norm_step_masked(qs_norm* h, float* obs /* [N,o] */, float* rew /* [N] */, const uint8_t* done /* [N] */, const uint8_t* active /* [N] or NULL */,
+                        float* term_obs /* [N,o] or NULL */, int training, int norm_obs, int norm_reward, float* raw_obs, float* raw_rew);
 
 /* qs_norm_step with everything a host-path step carries.  The arrays of the step (device memory): obs [N,o], rew [N], done [N], trunc [N]
  * (may be NULL), term_obs [N,o] (may be NULL), tail_rows = the compact list of the step's terminal observations, [tail_cap][1 + o] (may
@@ -588,7 +607,7 @@ const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way, and so were the qs_ars_* entries, ARS's bookkeeping.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way, and so were the qs_ars_* entries, ARS's bookkeeping, and qs_step_masked and qs_norm_step_masked, the per-environment pause.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 9
 int qs_abi_version(void);
 

@@ -195,9 +195,14 @@ enum { QS_PUSH_F = 8, QS_PUSH_REM = 6, QS_PUSH_FRAME = 7 };
 // rule that set the flag says; whoever steps e writes moved_wr[e] (and the list) for the next launch.  Flags alternate between two
 // arrays, lists and their fill counts (CTL_SOLO_CNT) rotate through three: launch i reads [i % 3], fills [(i + 1) % 3], clears the count of
 // [(i + 2) % 3].  F = 0: no solo waves, nothing of this is read or written.
+// `active` (qs_step_masked; null: none): environment e with active[e] == 0 is FROZEN -- nobody steps it in this launch ("exactly one" above
+// becomes "at most one").  Its home wave writes its outputs (the last observation, reward 0, flags 0) and moved_wr[e] = 0, so that it is its
+// home wave's again in the next launch and no list carries it over; its quad then gets the parked record like a moved one and stores nothing.
+// A home wave without an active environment leaves before the tile load, a solo wave whose environment is frozen at once.
 #define QS_SOLO_MAX 512
 struct SoloWaves { const float* parked;   // the handle's parked record (also the tail quads' of a partial wave); null: none
-                   const int* moved_rd; int* moved_wr; const int* list_rd; int* list_wr; int F, rd, wr, clr; float reach; };
+                   const int* moved_rd; int* moved_wr; const int* list_rd; int* list_wr; int F, rd, wr, clr; float reach;
+                   const uint8_t* active; };
 enum { CTL_SETTLE_SUBSTEPS = 0, CTL_RESETS = 1, CTL_SERVED = 2, CTL_SETTLED = 3, CTL_BACKLOG = 4, CTL_STALLS = 6,
        CTL_R = 8 /* one per cohort */, CTL_TERM_CNT = 8 + QS_COHORTS /* two */, CTL_DEV = 10 + QS_COHORTS /* QS_DEVCTR_*: the rare paths' telemetry */,
        /* (CTL_DEV + 2 .. + 11: the counting builds' counters, qs_core.h, tools/probe_*.py) */
@@ -313,7 +318,9 @@ __global__ __launch_bounds__(QS_WAVE, 1) void k_init(const qs_config* __restrict
 // SOFT: the build for handles with cfg.payload_soft whose common-path part holds the payload block's rows (qs_core.h; implicit cone only)
 // RACK: the build for handles with a rack (qs_rack; its common-path part holds the rack's rows under the implicit cone, SOFT = CONE): the
 // records' block slots (RK_*) travel with the tile
-template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ __forceinline__ void step_body(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
+// MASKED: the build that reads SoloWaves::active (qs_step_masked).  The unmasked kernels hold none of it: with the flag read at run time in
+// one kernel, the headline lost 0.75 % to another register allocation of the cold code (profiles/active_mask.md).
+template <bool CONE, int WAVES, bool SOFT, bool RACK = false, bool MASKED = false> static __device__ __forceinline__ void step_body(const qs_config* __restrict__ cfgp, float* __restrict__ recs,
                                                  const float* __restrict__ actions, float* __restrict__ obs_out,
                                                  float* __restrict__ rew_out, uint8_t* __restrict__ done_out,
                                                  uint8_t* __restrict__ trunc_out, float* __restrict__ obs_keep,
@@ -331,6 +338,7 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     // solo waves (SoloWaves): only in the one-wave-per-SIMD kernels without rack or soft payload; F = 0 elsewhere, and all of it folds away
     const int F = (WAVES == 1 && !SOFT && !RACK) ? solo.F : 0;
     const bool solo_wave = (int)blockIdx.x < F;                          // wave-uniform
+    const uint8_t* const active = MASKED ? solo.active : nullptr;        // SoloWaves::active; folds away in the unmasked kernels
     const int bid = (int)blockIdx.x - F;                                 // the workgroup's place among the environments' waves and the settle lanes
     // (a solo wave reads the second copy of the configuration, QsDevCfg::solo = 1: qs_lane.h, count_rare_path)
     const qs_config& cfg = solo_wave ? reinterpret_cast<const QsDevCfg*>(cfgp)[1].cfg : *cfgp;
@@ -347,6 +355,7 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
         if ((unsigned long long)blockIdx.x >= cnt) return;
         solo_env = solo.list_rd[blockIdx.x];
         if ((unsigned)solo_env >= (unsigned)cfg.n_envs) return;          // (never: the list holds what a step of this handle wrote)
+        if (active != nullptr && active[solo_env] == 0) return;          // frozen: nobody steps it
     }
     const bool settling = bid >= lanes.n_env_waves;                      // wave-uniform: this workgroup settles staging records
     const int sw = bid - lanes.n_env_waves;                              // settle lanes: which of them
@@ -364,6 +373,20 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     const int slot = threadIdx.x >> 2;
     const int env = first + slot;
     const int d = cfg.action_dim, od = cfg.obs_dim;
+    // frozen environments (SoloWaves::active): their outputs are written here, by the home wave, whoever would have stepped them; a wave
+    // that is left with nobody to step goes before it has asked for anything but the mask
+    bool frozen = false;
+    if (active != nullptr && !settling && !solo_wave) {                  // wave-uniform
+        frozen = env < limit && active[env] == 0;
+        if (frozen) {
+            quad_row_store(obs_out + (size_t)env * od, obs_keep + (size_t)env * od, od);
+            if ((threadIdx.x & 3) == 0) {
+                rew_out[env] = 0.0f; done_out[env] = 0; trunc_out[env] = 0;
+                if (F > 0) solo.moved_wr[env] = 0;
+            }
+        }
+        if (!__any(env < limit && !frozen)) return;
+    }
     QS_PHASE(26)
     // the quad of an environment fetches its action row (lane l takes entries l, l + 4, l + 8) -- issued before the tile loads, whose
     // latency then covers it
@@ -379,7 +402,8 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
             if (k < d && env < limit) a_pre[j] = actions[(size_t)env * d + k];
         }
         if (F > 0 && !solo_wave && env < limit) moved = solo.moved_rd[env];
-        if (push.rows && env < limit) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
+        if (frozen) moved = 1;                                           // (nobody's: its quad steps the parked record, its push does not count down)
+        if (push.rows && env < limit && !frozen) p_rem = push.rows[(size_t)env * QS_PUSH_F + QS_PUSH_REM];
     } else job = lanes.stage_jobs[env < limit ? env : first];
     const bool spawn = settling && lanes.spawn[cohort], last = settling && lanes.last[cohort];
     const int load_extent = settling ? (spawn ? 0 : ((RACK || cfg.payload_soft) ? (int)TILE_ALL : (int)QS_SETTLE_END)) : (RACK ? (int)TILE_ALL : tile_extent(cfg, false));
@@ -388,8 +412,9 @@ template <bool CONE, int WAVES, bool SOFT, bool RACK = false> static __device__ 
     if (load_extent > 0) tile_load(s_rec, base, first, limit, load_extent, ls, settling ? nullptr : solo.parked);
     if (spawn || last) zero_tile_tail(s_rec, load_extent, ls);
     const bool valid = env < limit && moved == 0;                        // this quad steps an environment (or a staging record) of its own
-    const unsigned long long not_mine = F > 0 ? __ballot(moved != 0) : 0ull;   // wave-uniform: slots that are a solo wave's
-    if (__builtin_expect(not_mine != 0ull, 0)) tile_park(s_rec, solo.parked, not_mine, load_extent, ls);
+    const unsigned long long not_mine = (F > 0 || active != nullptr) ? __ballot(moved != 0) : 0ull;   // wave-uniform: slots that are a solo wave's, or frozen
+    // (a handle without a parked record -- reset_lookahead = 0, QS_RAND_KEEP -- has frozen quads only: they step a private copy of their own record)
+    if (__builtin_expect(not_mine != 0ull && (!MASKED || solo.parked != nullptr), 0)) tile_park(s_rec, solo.parked, not_mine, load_extent, ls);
     QS_PHASE(27)
     if (!settling) {   // (a quad on the parked record holds the pose it was parked in: the settle action)
 #pragma unroll
@@ -537,6 +562,11 @@ template <bool CONE, bool SOFT> __global__ __launch_bounds__(QS_WAVE, 2) void k_
 // the same two for handles with a rack (qs_rack)
 template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_step_rack(QS_STEP_ARGS) { step_body<CONE, 1, CONE, true>(QS_STEP_PASS); }
 template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 2) void k_step_dense_rack(QS_STEP_ARGS) { step_body<CONE, 2, CONE, true>(QS_STEP_PASS); }
+// the four with an active mask (qs_step_masked; no soft-payload build: refused there)
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_step_masked(QS_STEP_ARGS) { step_body<CONE, 1, false, false, true>(QS_STEP_PASS); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 2) void k_step_dense_masked(QS_STEP_ARGS) { step_body<CONE, 2, false, false, true>(QS_STEP_PASS); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_step_rack_masked(QS_STEP_ARGS) { step_body<CONE, 1, CONE, true, true>(QS_STEP_PASS); }
+template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 2) void k_step_dense_rack_masked(QS_STEP_ARGS) { step_body<CONE, 2, CONE, true, true>(QS_STEP_PASS); }
 
 // Settle lanes, between two settles of a cohort (an epoch = the launches one settle takes): the staging records that finished settling go
 // to the look-ahead slots of their environments (R_EPISODE marks the slot as holding that episode) ...
@@ -720,11 +750,12 @@ template <bool CONE> __global__ __launch_bounds__(QS_WAVE, 1) void k_lookahead_f
 // The parked record of a handle (qs_create): environment 0's settled state of episode 0 out of its look-ahead slot -- a whole record as a
 // reset leaves it, filter history and last action at the settle action -- lifted 5 m, at rest.  A quad that steps it under the settle
 // action touches nothing and reaches no joint stop within an env step, so it never asks for a rare path; it is loaded fresh by every
-// launch and never stored.
-__global__ void k_make_parked(const float* __restrict__ slot, float* __restrict__ parked) {
+// launch and never stored.  lift = 0 on a handle with a rack: its robots are reset hanging from the anchor, which is where the parked one stays
+// (lifted, its rack would pull it back over metres in every launch).
+__global__ void k_make_parked(const float* __restrict__ slot, float* __restrict__ parked, float lift) {
     for (int i = threadIdx.x; i < QS_REC; i += blockDim.x) {
         float v = i < QS_REC_END ? slot[i] : 0.0f;
-        if (i == R_POS + 2) v += 5.0f;
+        if (i == R_POS + 2) v += lift;
         if ((i >= R_VLIN && i < R_VLIN + 3) || (i >= R_VANG && i < R_VANG + 3) || (i >= R_QD && i < R_QD + 12) || (i >= R_WARM && i < R_WARM + 4)) v = 0.0f;
         parked[i] = v;
     }
@@ -976,7 +1007,7 @@ static int create_impl(const qs_config* cfg, const qs_rack* rack, int device, qs
         QS_HIP(hipMalloc(&h->d_solo_list, 3 * QS_SOLO_MAX * sizeof(int)));
         QS_HIP(hipMemsetAsync(h->d_moved, 0, 2 * n * sizeof(int), h->stream));
         QS_HIP(hipMemsetAsync(h->d_solo_list, 0, 3 * QS_SOLO_MAX * sizeof(int), h->stream));
-        hipLaunchKernelGGL(k_make_parked, dim3(1), dim3(256), 0, h->stream, h->la.slots, h->d_parked);
+        hipLaunchKernelGGL(k_make_parked, dim3(1), dim3(256), 0, h->stream, h->la.slots, h->d_parked, h->rack.on ? 0.0f : 5.0f);
         QS_HIP(hipGetLastError());
         const char* sv = getenv("QS_SOLO_WAVES");
         const char* rv = getenv("QS_SOLO_REACH");
@@ -1090,11 +1121,20 @@ int qs_solo_waves(qs_handle* h, int f, float reach) {
     return 0;
 }
 
-static int launch_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc);
+static int launch_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc, const uint8_t* active = nullptr);
 
 int qs_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
     if (!h || !actions || !obs || !rew || !done || !trunc) QS_FAIL(-1, "null argument");
     return launch_step(h, actions, obs, rew, done, trunc);
+}
+
+int qs_step_masked(qs_handle* h, const float* actions, const uint8_t* active, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
+    if (!h || !actions || !obs || !rew || !done || !trunc) QS_FAIL(-1, "null argument");
+    // the parked record that frozen quads step lifts the trunk and leaves the payload block where it was: the block's fixed constraint would
+    // start every launch five metres apart, which is a rare path in every substep
+    if (active && h->cfg.payload_soft)
+        QS_FAIL(-1, "qs_step_masked: an active mask is not supported with payload_soft (the parked record of frozen environments does not carry the payload block along); step without a mask");
+    return launch_step(h, actions, obs, rew, done, trunc, active);
 }
 
 int qs_step_fused(qs_handle* h, const float* actions, float* fused) {
@@ -1102,7 +1142,7 @@ int qs_step_fused(qs_handle* h, const float* actions, float* fused) {
     return launch_step(h, actions, fused, nullptr, nullptr, nullptr);   // a null reward pointer selects the fused row layout in the kernel
 }
 
-static int launch_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc) {
+static int launch_step(qs_handle* h, const float* actions, float* obs, float* rew, uint8_t* done, uint8_t* trunc, const uint8_t* active) {
     QS_ON_DEVICE(h);
     SettleLanes lanes;
     memset(&lanes, 0, sizeof(lanes));
@@ -1140,6 +1180,7 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
     SoloWaves solo;
     memset(&solo, 0, sizeof(solo));
     solo.parked = h->d_parked;
+    solo.active = active;
     if (F > 0) {
         const long long i = h->solo_tick++;
         solo.F = F; solo.rd = (int)(i % 3); solo.wr = (int)((i + 1) % 3); solo.clr = (int)((i + 2) % 3); solo.reach = h->solo_reach;
@@ -1187,7 +1228,10 @@ static int launch_step(qs_handle* h, const float* actions, float* obs, float* re
                            h->d_obs, h->d_term_obs, h->la, h->d_stats, lanes, tap, demo, tail, push, solo);
     };
     qs::with_build(build, [&](auto cone, auto soft, auto rack) {
-        if constexpr (rack()) launch(dense ? k_step_dense_rack<cone()> : k_step_rack<cone()>);
+        if (active) {   // (never with the soft payload: qs_step_masked refuses it)
+            if constexpr (rack()) launch(dense ? k_step_dense_rack_masked<cone()> : k_step_rack_masked<cone()>);
+            else launch(dense ? k_step_dense_masked<cone()> : k_step_masked<cone()>);
+        } else if constexpr (rack()) launch(dense ? k_step_dense_rack<cone()> : k_step_rack<cone()>);
         else launch(dense ? k_step_dense<cone(), soft()> : k_step<cone(), soft()>);
     });
     QS_HIP(hipGetLastError());

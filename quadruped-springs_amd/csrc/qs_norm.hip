@@ -50,8 +50,11 @@ struct Moments { double n, mean, m2; };
 // Batch moments: block b reduces rows [b * rows_per_block, ...), every column at once -- thread (cx, ry) takes column c0 + cx of rows ry,
 // ry + 8, ...: a wavefront reads two whole rows (coalesced).  The returns column (index o) also advances VecNormalize.returns
 // (vec_normalize.py:_update_reward).
+// `active` (qs_norm_step_masked; null: every row): rows with active[i] == 0 are not counted and their return does not advance.  The pivot
+// stays row r0 whatever its flag (any value of the column serves), so a mask of ones gives the bits of no mask.
 __global__ __launch_bounds__(256) void k_norm_moments(const float* __restrict__ obs, const float* __restrict__ rew, double* __restrict__ ret, int n, int o,
-                                                      double gamma, int with_obs, int with_ret, int rows_per_block, Moments* __restrict__ part) {
+                                                      double gamma, int with_obs, int with_ret, int rows_per_block, Moments* __restrict__ part,
+                                                      const uint8_t* __restrict__ active) {
     const int C = o + 1, cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
     const int r0 = blockIdx.x * rows_per_block, r1 = min(n, r0 + rows_per_block);
     __shared__ double sh[3][8][33];
@@ -62,8 +65,9 @@ __global__ __launch_bounds__(256) void k_norm_moments(const float* __restrict__ 
         double s1 = 0.0, s2 = 0.0, cnt = 0.0, p = 0.0;
         for (int k0 = 0; k0 * 8 < rows_per_block; k0 += QN_CH) {
             double x[QN_CH];
+            bool on[QN_CH];     // the row exists and is counted
 #pragma unroll
-            for (int k = 0; k < QN_CH; k++) x[k] = 0.0;
+            for (int k = 0; k < QN_CH; k++) { const int i = r0 + ry + 8 * (k0 + k); x[k] = 0.0; on[k] = i < r1 && (active == nullptr || active[i] != 0); }
             if (act && c < o) {
                 float v[QN_CH];
 #pragma unroll
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void k_norm_moments(const float* __restrict__ 
 #pragma unroll
                 for (int k = 0; k < QN_CH; k++) { const int i = r0 + ry + 8 * (k0 + k); q[k] = i < r1 ? ret[i] : 0.0; v[k] = i < r1 ? rew[i] : 0.0f; }
 #pragma unroll
-                for (int k = 0; k < QN_CH; k++) { x[k] = q[k] * gamma + (double)v[k]; if (r0 + ry + 8 * (k0 + k) < r1) ret[r0 + ry + 8 * (k0 + k)] = x[k]; }
+                for (int k = 0; k < QN_CH; k++) { x[k] = q[k] * gamma + (double)v[k]; if (on[k]) ret[r0 + ry + 8 * (k0 + k)] = x[k]; }
             }
             if (k0 == 0) {   // the pivot: row r0 of the column (thread ry = 0 holds it in x[0])
                 if (ry == 0) piv[cx] = x[0];
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(256) void k_norm_moments(const float* __restrict__ 
             if (act) {
 #pragma unroll
                 for (int k = 0; k < QN_CH; k++)
-                    if (r0 + ry + 8 * (k0 + k) < r1) { const double d = x[k] - p; s1 += d; s2 += d * d; cnt += 1.0; }
+                    if (on[k]) { const double d = x[k] - p; s1 += d; s2 += d * d; cnt += 1.0; }
             }
         }
         sh[0][ry][cx] = cnt; sh[1][ry][cx] = s1; sh[2][ry][cx] = s2;
@@ -103,9 +107,13 @@ __global__ __launch_bounds__(256) void k_norm_moments(const float* __restrict__ 
 // running_mean_std.py update_from_moments + vec_normalize.py normalize_obs (incl. terminal observations), normalize_reward,
 // returns[dones] = 0.  training: EVERY block adds up the blocks' moments (the same sums in the same order: the same bits) and folds the
 // batch into the statistics it reads from `stat`; block 0 stores the result in `stat_next`.  Then each block normalises its own rows.
+// `active` (null: every row): the batch count is the number of rows k_norm_moments counted, summed here (without a mask that sum is n, which
+// the host passes); a batch of no rows leaves the statistics as they are; only active rows' returns go to zero at an episode's end.  Every
+// row, counted or not, is normalised.
 __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __restrict__ ret, int n, int o, const double* __restrict__ stat, double* __restrict__ stat_next,
                                                      const Moments* __restrict__ part, int n_parts, int rows_per_block, double batch_count, double eps,
-                                                     double clip_obs, double clip_rew, int training, int with_obs, int with_ret, int norm_obs, int norm_rew) {
+                                                     double clip_obs, double clip_rew, int training, int with_obs, int with_ret, int norm_obs, int norm_rew,
+                                                     const uint8_t* __restrict__ active) {
     float* const obs = io.obs; float* const term_obs = io.term_obs; float* const rew = io.rew; const uint8_t* const done = io.done;
     float* const raw_obs = io.raw_obs; float* const raw_rew = io.raw_rew;
     float* const obs_to = io.out_obs ? io.out_obs : io.obs; float* const rew_to = io.out_rew ? io.out_rew : io.rew;     // (in place unless told otherwise)
@@ -114,6 +122,7 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
     __shared__ double sh[3][8][33];
     __shared__ double s_mean[256], s_inv[256];
     __shared__ double s_rvar;      // variance of the returns (column o) after this step's update
+    __shared__ double s_bc[2];     // rows in the batch: of the observations (column 0), of the returns (column o)
     for (int c0 = 0; c0 < C; c0 += 32) {
         const int c = c0 + cx, cc = c < C ? c : 0;
         const bool upd = training && c < C && ((c < o && with_obs) || (c == o && with_ret));
@@ -134,12 +143,15 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
 #pragma unroll
                 for (int k = 1; k < 8; k++) { S0 += sh[0][k][cx]; S1 += sh[1][k][cx]; S2 += sh[2][k][cx]; }
                 double mean = stat[c], var = stat[C + c], bm = stat[2 * C + 2 + c], bv = stat[3 * C + 2 + c], inv = stat[4 * C + 2 + c];
-                if (upd) {
+                const double bc = active != nullptr ? S0 : batch_count;
+                if (c == 0) s_bc[0] = bc;
+                if (c == o) s_bc[1] = bc;
+                if (upd && bc > 0.0) {
                     bm = P + S1 / S0; bv = (S2 - S1 * S1 / S0) / S0;
                     const double count = stat[2 * C + (c == o ? 1 : 0)];
-                    const double delta = bm - mean, tot = count + batch_count;
-                    const double new_var = (var * count + bv * batch_count + delta * delta * count * batch_count / (count + batch_count)) / (count + batch_count);
-                    mean = mean + delta * batch_count / tot;
+                    const double delta = bm - mean, tot = count + bc;
+                    const double new_var = (var * count + bv * bc + delta * delta * count * bc / (count + bc)) / (count + bc);
+                    mean = mean + delta * bc / tot;
                     var = new_var;
                     inv = 1.0 / sqrt(new_var + eps);
                 }
@@ -151,7 +163,7 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
         } else if (ry == 0 && c < C) { s_mean[c] = stat[c]; s_inv[c] = stat[4 * C + 2 + c]; if (c == o) s_rvar = stat[C + c]; }
     }
     if (training && blockIdx.x == 0 && threadIdx.x < 2)
-        stat_next[2 * C + threadIdx.x] = stat[2 * C + threadIdx.x] + ((threadIdx.x == 0 ? with_obs : with_ret) ? batch_count : 0.0);
+        stat_next[2 * C + threadIdx.x] = stat[2 * C + threadIdx.x] + ((threadIdx.x == 0 ? with_obs : with_ret) ? s_bc[threadIdx.x] : 0.0);
     __syncthreads();
     const int rows = r1 - r0;
     if (rows <= 0) return;
@@ -202,7 +214,7 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
             if (raw_rew) raw_rew[i] = x;
             if (norm_rew) rew_to[i] = (float)fmin(fmax((double)x / rstd, -clip_rew), clip_rew);
             else if (io.out_rew) rew_to[i] = x;
-            if (done && done[i]) ret[i] = 0.0;
+            if (done && done[i] && (active == nullptr || active[i] != 0)) ret[i] = 0.0;
         }
     }
 }
@@ -279,13 +291,13 @@ int qs_norm_get_stats(qs_norm* h, double* obs_mean, double* obs_var, double* obs
 }
 
 // the two launches of a step / reset: batch moments (training only), then fold + normalise
-static int norm_launch(qs_norm* h, const qs_norm_io& io, int training, int with_obs, int with_ret, int norm_obs, int norm_reward) {
+static int norm_launch(qs_norm* h, const qs_norm_io& io, int training, int with_obs, int with_ret, int norm_obs, int norm_reward, const uint8_t* active = nullptr) {
     if (training)
         hipLaunchKernelGGL(k_norm_moments, dim3(h->n_parts), dim3(256), 0, h->stream, io.obs, io.rew, h->d_ret, h->n, h->o, h->gamma, with_obs, with_ret,
-                           h->rows_per_block, (Moments*)h->d_part);
+                           h->rows_per_block, (Moments*)h->d_part, active);
     hipLaunchKernelGGL(k_norm_finish, dim3(h->n_parts), dim3(256), 0, h->stream, io, h->d_ret, h->n, h->o, QN_STAT(h, h->cur), QN_STAT(h, h->cur ^ 1),
                        (const Moments*)h->d_part, h->n_parts, h->rows_per_block, (double)h->n, h->eps, h->clip_obs, h->clip_rew,
-                       training, with_obs, with_ret, norm_obs, norm_reward);
+                       training, with_obs, with_ret, norm_obs, norm_reward, active);
     QS_HIP(hipGetLastError());
     if (training) h->cur ^= 1;
     return 0;
@@ -339,6 +351,16 @@ int qs_norm_step(qs_norm* h, float* obs, float* rew, const uint8_t* done, float*
     memset(&io, 0, sizeof(io));
     io.obs = obs; io.rew = rew; io.done = done; io.term_obs = term_obs; io.raw_obs = raw_obs; io.raw_rew = raw_rew;
     return qs_norm_step_io(h, &io, training, norm_obs, norm_reward);
+}
+
+int qs_norm_step_masked(qs_norm* h, float* obs, float* rew, const uint8_t* done, const uint8_t* active, float* term_obs, int training, int norm_obs,
+                        int norm_reward, float* raw_obs, float* raw_rew) {
+    if (!h || !obs || !rew || !done) QS_FAIL(-1, "null argument");
+    qs_norm_io io;
+    memset(&io, 0, sizeof(io));
+    io.obs = obs; io.rew = rew; io.done = done; io.term_obs = term_obs; io.raw_obs = raw_obs; io.raw_rew = raw_rew;
+    QS_ON_DEVICE(h);
+    return norm_launch(h, io, training ? 1 : 0, norm_obs, 1, norm_obs, norm_reward, active);
 }
 
 }  // extern "C"

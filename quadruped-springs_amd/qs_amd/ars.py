@@ -32,13 +32,27 @@ def _auto_reset_of(env):
     return None
 
 
+def _takes_active(env):
+    """whether env.step_tensor has the active= keyword (QuadrupedVecEnv, DeviceVecNormalize)"""
+    import inspect
+    try:
+        return "active" in inspect.signature(env.step_tensor).parameters
+    except (AttributeError, TypeError, ValueError):
+        return False
+
+
 class DeviceARS:
     """ARS over a QuadrupedVecEnv or a DeviceVecNormalize around one.  `policy` is a DevicePolicy(num_envs=N, n_policies=2 n_delta) (anything
     with n_params, n_policies, num_envs, device and set_params).  env may be None for a learner that is only handed rewards and dones
     (begin / account / finish)."""
 
     def __init__(self, env, policy, n_delta=8, n_top=None, learning_rate=0.02, delta_std=0.05, zero_policy=True, alive_bonus_offset=0.0,
-                 episodes_per_env=1, horizon=300, check_every=16, seed=0):
+                 episodes_per_env=1, horizon=300, check_every=16, seed=0, freeze_done=False):
+        """freeze_done=True: rollout() steps with active = the environments still alive (step_tensor(active=)), so a robot whose episodes
+        are over is no longer stepped -- it lies on the floor, on the slow many-rows contact path, and every launch waits for its slowest
+        wave.  The accounts ignore dead environments either way: on an environment without observation normalisation in training mode the
+        per-environment returns and lengths, the candidates' returns, idx, w and theta are the same bits as with freeze_done=False.  Under a
+        DeviceVecNormalize(training=True) the running statistics then see living robots only, so the results differ by design."""
         import torch
         self.torch = torch
         self.env, self.policy = env, policy
@@ -65,6 +79,9 @@ class DeviceARS:
                 raise ValueError(f"episodes_per_env = {self.episodes_per_env} needs an environment with auto_reset=True (an environment that is not reset "
                                  "has no second episode)")
         self.learning_rate, self.delta_std, self.alive_bonus_offset = float(learning_rate), float(delta_std), float(alive_bonus_offset)
+        self.freeze_done = bool(freeze_done)
+        if self.freeze_done and env is not None and not _takes_active(env):
+            raise ValueError(f"freeze_done=True needs an environment whose step_tensor takes active= ({type(env).__name__}.step_tensor does not)")
         self.device = policy.device
         if self.device.type != "cuda":
             raise ValueError(f"policy.device = {self.device}: DeviceARS has no CPU path")
@@ -167,9 +184,9 @@ class DeviceARS:
         _lib.check(self.lib.qs_ars_finish(self.h, C.c_void_p(self.theta.data_ptr()), p, self.n_top, self.learning_rate, self.alive_bonus_offset))
 
     # ---- sb3_contrib's surface
-    def _step(self, actions):
+    def _step(self, actions, active=None):
         """-> (obs, raw reward, done): DevicePPO._step's rule for the raw reward"""
-        obs, rew, done, _ = self.env.step_tensor(actions)
+        obs, rew, done, _ = self.env.step_tensor(actions) if active is None else self.env.step_tensor(actions, active=active)
         return obs, (self.env.old_reward if self._normalised else rew), done
 
     def rollout(self):
@@ -181,7 +198,8 @@ class DeviceARS:
         self.begin()
         steps = 0
         while steps < self.horizon:
-            obs, raw, done = self._step(self.policy.act(obs))
+            # (freeze_done: the alive flags as the previous step's account left them, a stream-ordered copy -- no wait)
+            obs, raw, done = self._step(self.policy.act(obs), self.get("alive") if self.freeze_done else None)
             self.account(raw, done)
             steps += 1
             if steps % self.check_every == 0 and self.alive() == 0:

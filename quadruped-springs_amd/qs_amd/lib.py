@@ -24,6 +24,7 @@ EXPORTS = (
     "qs_ppo_create", "qs_ppo_destroy", "qs_ppo_set_stream", "qs_ppo_bind", "qs_ppo_grad", "qs_ppo_adam", "qs_ppo_refusals",
     "qs_ars_create", "qs_ars_destroy", "qs_ars_set_stream", "qs_ars_perturb", "qs_ars_begin", "qs_ars_account", "qs_ars_alive", "qs_ars_returns",
     "qs_ars_finish", "qs_ars_get",
+    "qs_step_masked", "qs_norm_step_masked",
 )
 
 
@@ -119,6 +120,9 @@ def load():
         lib.qs_render_states.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp, vp]
     if hasattr(lib, "qs_solo_waves"):   # (added under ABI 9; an older library under QS_LIB_PATH lacks it)
         lib.qs_solo_waves.argtypes = [vp, i32, C.c_float]
+    if hasattr(lib, "qs_step_masked"):   # (added under ABI 9; an older library under QS_LIB_PATH lacks them)
+        lib.qs_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.qs_norm_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.qs_counter.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
     lib.qs_counters_async.argtypes = [vp, vp]
     f32, f64, pd = C.c_float, C.c_double, C.POINTER(C.c_double)

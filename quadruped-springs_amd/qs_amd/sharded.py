@@ -58,6 +58,14 @@ class ShardedVecEnv:
         self._all_gather(g)
         return self._unpack(g)[0]
 
+    def step_tensor(self, actions=None, active=None):
+        """step() under the name the local environments use.  A per-environment pause (QuadrupedVecEnv.step_tensor(active=)) is not
+        available here: the shards step through the fused row (qs_step_fused), which takes no mask."""
+        if active is not None:
+            raise NotImplementedError("ShardedVecEnv steps through the fused row (step_fused), which takes no active mask: step the shards' "
+                                      "QuadrupedVecEnv.step_tensor(active=) directly, or step without a mask")
+        return self.step(actions)
+
     def step(self, actions=None, out=None, unpack=True):
         """`actions`: the global [N, d] batch on the learner rank (ignored elsewhere).  `out` (optional): a contiguous float32
         [N, o + 2] tensor that receives the gathered rows (e.g. one row block of the learner's rollout buffer) instead of the

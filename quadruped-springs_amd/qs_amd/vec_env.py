@@ -20,6 +20,22 @@ PARAM = dict(mu=0, spring_k=1, spring_b=2, kp=3, kd=4, all=5)
 FRAME = dict(link=1, world=2)   # QS_FRAME_LINK / QS_FRAME_WORLD = pybullet.LINK_FRAME / WORLD_FRAME
 
 
+def active_mask(active, num_envs, device):
+    """step_tensor's `active` as the contiguous uint8 [N] tensor the step kernel reads: a bool or uint8 tensor of shape [num_envs] on
+    `device`; anything else raises ValueError before any launch"""
+    import torch
+    if not torch.is_tensor(active):
+        raise ValueError(f"active must be a bool or uint8 torch tensor of shape {(num_envs,)} on {device}, got {type(active).__name__}")
+    if active.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"active must be a bool or uint8 tensor, got {active.dtype}")
+    if tuple(active.shape) != (num_envs,):
+        raise ValueError(f"active must have shape {(num_envs,)}, got {tuple(active.shape)}")
+    if active.device != torch.device(device):
+        raise ValueError(f"active is on {active.device}, the environments on {device}")
+    a = active.contiguous()
+    return a.view(torch.uint8) if a.dtype == torch.bool else a
+
+
 class QuadrupedVecEnv(SB3VecEnv):
     def __init__(self, num_envs=1, device=0, auto_reset=True, reset_lookahead=None, copy_outputs=True, solo_waves=None, solo_reach=None, **env_kwargs):
         """reset_lookahead = K: every environment keeps the settled reset states of its next K episodes ready (computed by extra workgroups
@@ -77,6 +93,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         self.copy_outputs = bool(copy_outputs)
         self._trace = None
         self._push_keep = None        # the inputs of the last apply_external_force, alive until its kernel has read them
+        self._active_keep = None      # the mask of the last step_tensor(active=), likewise
         self.render_mode = None
         self.render_indices = None        # environments get_images / render draw (None = all, as SB3 renders every sub-environment)
         self.render_size = DEFAULT_SIZE   # (width, height)
@@ -163,15 +180,27 @@ class QuadrupedVecEnv(SB3VecEnv):
         _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
         return self._obs
 
-    def step_tensor(self, actions):
-        """actions: float32 CUDA tensor [N, action_dim] -> (obs, rew, done, truncated) CUDA tensors (reused buffers)."""
+    def step_tensor(self, actions, active=None):
+        """actions: float32 CUDA tensor [N, action_dim] -> (obs, rew, done, truncated) CUDA tensors (reused buffers).
+        active: a bool or uint8 tensor [N] on the handle's device, None for none (qs_step_masked).  An environment with active[e] == 0 is
+        frozen for this step: nobody steps it, nothing of it changes (record, pending push, look-ahead window, counters), no reset happens
+        to it; its row of obs is its last observation, its reward 0, done and truncated 0.  The active ones get the bits they get without a
+        mask.  A wave of 16 consecutive environments that are all frozen costs the launch next to nothing, and a frozen robot that lies on
+        the floor keeps no wave-mate waiting.  Handles without a parked record (reset_lookahead=0, KEEP randomizer) are correct and no
+        faster; payload="soft" handles refuse a mask."""
         a = actions
         if a.dtype != self.torch.float32 or not a.is_contiguous() or a.device != self.device:
             a = a.to(device=self.device, dtype=self.torch.float32).contiguous()
         if a.shape != (self.num_envs, self.action_dim):
             raise ValueError(f"actions must have shape {(self.num_envs, self.action_dim)}, got {tuple(a.shape)}")
+        m = None if active is None else active_mask(active, self.num_envs, self.device)
         self._stream()
-        _lib.check(self.lib.qs_step(self.h, self._ptr(a), self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done), self._ptr(self._trunc)))
+        if m is None:
+            _lib.check(self.lib.qs_step(self.h, self._ptr(a), self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done), self._ptr(self._trunc)))
+        else:
+            _lib.check(self.lib.qs_step_masked(self.h, self._ptr(a), self._ptr(m), self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done),
+                                               self._ptr(self._trunc)))
+        self._active_keep = m
         return self._obs, self._rew, self._done, self._trunc
 
     def step_fused(self, actions, out):

@@ -43,12 +43,22 @@ class DeviceVecNormalize:
         _lib.check(self.lib.qs_norm_reset(self.h, self._p(obs), int(self.training), int(self.norm_obs)))
         return obs
 
-    def step_tensor(self, actions, terminal_obs=None):
+    def step_tensor(self, actions, terminal_obs=None, active=None):
         """-> (obs, rew, done, truncated): normalised in place in the environment's reused buffers; the raw values of this step
         stay in `old_obs` / `old_reward` (VecNormalize.get_original_obs / get_original_reward).  terminal_obs: a float32 [N, obs_dim]
         tensor on the device that receives the step's terminal observations (get_info("terminal_obs")) normalised with this step's
-        statistics, as VecNormalize.step_wait normalises infos[i]["terminal_observation"]."""
-        obs, rew, done, trunc = self.venv.step_tensor(actions)
+        statistics, as VecNormalize.step_wait normalises infos[i]["terminal_observation"].
+        active: the environment's step_tensor(active=) mask (qs_norm_step_masked).  With training=True the batch moments of observations and
+        returns are taken over the active rows only, the batch count is their number, and only their returns advance and are cleared at
+        done; a step without an active row updates nothing.  Every row, frozen ones included, is normalised with the step's statistics, and
+        old_obs / old_reward hold every row."""
+        if active is None:
+            obs, rew, done, trunc = self.venv.step_tensor(actions)
+            m = None
+        else:
+            from .vec_env import active_mask
+            m = active_mask(active, self.num_envs, self.device)
+            obs, rew, done, trunc = self.venv.step_tensor(actions, active=m)
         p_term = None
         if terminal_obs is not None:
             t = self.torch
@@ -59,8 +69,12 @@ class DeviceVecNormalize:
             p_term = self._p(terminal_obs)
             _lib.check(self.lib.qs_get_info(self.venv.h, INFO["terminal_obs"], p_term))      # (on the stream venv.step_tensor has just set)
         self._stream()
-        _lib.check(self.lib.qs_norm_step(self.h, self._p(obs), self._p(rew), self._p(done), p_term, int(self.training), int(self.norm_obs),
-                                         int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
+        if m is None:
+            _lib.check(self.lib.qs_norm_step(self.h, self._p(obs), self._p(rew), self._p(done), p_term, int(self.training), int(self.norm_obs),
+                                             int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
+        else:
+            _lib.check(self.lib.qs_norm_step_masked(self.h, self._p(obs), self._p(rew), self._p(done), self._p(m), p_term, int(self.training),
+                                                    int(self.norm_obs), int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
         return obs, rew, done, trunc
 
     def normalize_obs(self, obs):
