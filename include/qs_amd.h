@@ -557,6 +557,39 @@ enum { QS_ARS_GET_RET = 0, QS_ARS_GET_LEN = 1, QS_ARS_GET_EPISODES = 2, QS_ARS_G
        QS_ARS_GET_RETURNS = 6, QS_ARS_GET_IDX = 7, QS_ARS_GET_W = 8, QS_ARS_GET_STATS = 9 };
 int qs_ars_get(qs_ars* h, int what, void* dev_out);
 
+/* ---- The sampling planner on the device (predictive sampling and MPPI over device forks, examples/mpc.py).  The arithmetic, its roundings, its
+ * summation order and its two own rules (ties go to the lower candidate, a score that is not finite counts as -inf) are csrc/qs_mpc.h.
+ * n_robots real robots are the environments [0, M); candidate c of robot m is environment M + m C + c, N = M (1 + C).  The handle owns the plan
+ * [M][H][d], the sampled sequences [H][M C][d], the candidates' scores and running flags [M C] and the last choice [M].  Every call is
+ * stream-ordered, waits for nothing and allocates nothing after create; there are no floating-point atomics, so the same inputs give the
+ * same bits. */
+typedef struct qs_mpc qs_mpc;
+enum { QS_MPC_BEST = 0, QS_MPC_MPPI = 1 };
+/* Refuses, with text in qs_last_error(): n_robots, n_candidates, horizon or action_dim < 1, n_candidates > 4096, horizon * action_dim > 1024,
+ * products that leave 31 bits.  The plan starts at zero. */
+int qs_mpc_create(int n_robots, int n_candidates, int horizon, int action_dim, int device, qs_mpc** out);
+void qs_mpc_destroy(qs_mpc* h);
+int qs_mpc_set_stream(qs_mpc* h, void* hip_stream);
+/* The sequences of a control step from eps [H][M C][d] (standard normal, filled by the caller): candidate 0 is the plan as it stands, the others
+ * clamp(plan + sigma * eps, -1, 1); every score 0, every candidate running.  Refuses a sigma that is not finite. */
+int qs_mpc_sample(qs_mpc* h, const float* eps, float sigma);
+/* Horizon step `step` = 0 .. H, one launch next to the environment step.  For step >= 1 it accounts the environment step before it from
+ * reward [N] and done [N]: a running candidate adds its reward, then stops running where done.  For step < H it copies the sequences' slab
+ * of that step into actions[M:] (actions [N][d]).  At step == H a candidate still running adds reward_end[(M + i) * reward_end_stride].
+ * active_or_null [N], where given, receives the candidates' running flags and 0 for the real robots (qs_step_masked's mask).  reward and
+ * done may be null at step 0, reward_end below step H. */
+int qs_mpc_feed(qs_mpc* h, int step, const float* reward, const uint8_t* done, const float* reward_end, int reward_end_stride, float* actions,
+                uint8_t* active_or_null);
+/* The choice: per robot the best candidate (QS_MPC_BEST) or the mean under the weights exp((score - max) / lambda) (QS_MPC_MPPI; refuses a
+ * lambda that is not positive and finite).  actions[m] = the chosen sequence's first action, the plan = the rest, the last action held. */
+int qs_mpc_finish(qs_mpc* h, int method, float lambda, float* actions);
+/* Getters: a stream-ordered copy into DEVICE memory.  PLAN float32 [M][H][d], SEQ float32 [H][M C][d], SCORE float32 [M C], RUNNING uint8
+ * [M C], BEST int32 [M] and BEST_SCORE float32 [M] of the last finish. */
+enum { QS_MPC_GET_PLAN = 0, QS_MPC_GET_SEQ = 1, QS_MPC_GET_SCORE = 2, QS_MPC_GET_RUNNING = 3, QS_MPC_GET_BEST = 4, QS_MPC_GET_BEST_SCORE = 5 };
+int qs_mpc_get(qs_mpc* h, int what, void* dev_out);
+/* The plans of the robots with mask_or_null[m] != 0 (null: all) become plan_or_null's rows [M][H][d] (null: zero). */
+int qs_mpc_set_plan(qs_mpc* h, const float* plan_or_null, const uint8_t* mask_or_null);
+
 /* ---- Device snapshots: save, restore and fork environments (what pybullet.saveState / restoreState are to the reference's simulator; the CPU
  * oracle's qso_snapshot / qso_restore).  A snapshot is one row of qs_snapshot_info::row_floats floats per environment, in DEVICE memory owned by
  * the caller (16-byte aligned): [the environment's whole record | its push row | its last observation | its terminal observation], layout in
@@ -607,7 +640,7 @@ const char* qs_version(void);
 /* Bumped whenever the meaning or type of an existing entry point's argument or of a struct field changes (a caller built against an older
  * header would pass garbage without any loader error): 5 = round 5 (qs_norm_create takes its four float arguments as double since round 4;
  * qs_config::reserved_f[0] became support_margin); 6 = qs_set_external_wrench, QS_INFO_EXTERNAL_WRENCH; 7 = qs_camera, qs_render, qs_render_states; 8 = qs_rack, qs_create_ex,
- * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way, and so were the qs_ars_* entries, ARS's bookkeeping, and qs_step_masked and qs_norm_step_masked, the per-environment pause.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
+ * qs_set_rack, QS_INFO_RACK.  (The qs_policy_* entries were added under 8: they change no existing entry point, argument or field.)  9 = qs_ac_*, qs_gae (PPO collection; additive, every earlier entry keeps its signature, so structs and calls written against 8 stay valid; qs_amd/lib.py keeps 8 as the version of its struct layouts and demands 9 of the library).  (qs_snapshot_info, qs_snapshot, qs_restore, qs_fork, qs_norm_get_returns and qs_norm_set_returns were added under 9, as the qs_policy_* entries under 8: they change no existing entry point, argument or field.)  (The qs_ppo_* entries and qs_ppo_hyper, the PPO update, were added under 9 in the same way, and so were the qs_ars_* entries, ARS's bookkeeping, and qs_step_masked and qs_norm_step_masked, the per-environment pause.; and the qs_mpc_* entries, the sampling planner.)  A binding compares it with the QS_ABI_VERSION of the header it was written against. */
 #define QS_ABI_VERSION 9
 int qs_abi_version(void);
 

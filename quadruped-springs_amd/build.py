@@ -18,6 +18,7 @@ SRC_PPO = os.path.join(HERE, "csrc", "qs_ppo.hip")
 SRC_PPO_TRAIN = os.path.join(HERE, "csrc", "qs_ppo_train.hip")
 SRC_SNAPSHOT = os.path.join(HERE, "csrc", "qs_snapshot.hip")
 SRC_ARS = os.path.join(HERE, "csrc", "qs_ars.hip")
+SRC_MPC = os.path.join(HERE, "csrc", "qs_mpc.hip")
 OUT = os.path.join(HERE, "qs_amd", "libqs_hip.so")
 
 
@@ -108,7 +109,7 @@ def build(force=False, verbose=False):
     vgpr_form = os.environ.get("QS_MFMA_VGPR_FORM", "1") != "0"
 
     def command(with_form):
-        c = [hipcc()] + hipcc_flags(with_form) + ['-DQS_SOURCE_SHA="' + source_fingerprint() + '"', "-I" + os.path.join(REPO, "include"), "-o", os.environ.get("QS_BUILD_OUT") or OUT, SRC, SRC_NORM, SRC_RENDER, SRC_POLICY, SRC_PPO, SRC_PPO_TRAIN, SRC_SNAPSHOT, SRC_ARS]
+        c = [hipcc()] + hipcc_flags(with_form) + ['-DQS_SOURCE_SHA="' + source_fingerprint() + '"', "-I" + os.path.join(REPO, "include"), "-o", os.environ.get("QS_BUILD_OUT") or OUT, SRC, SRC_NORM, SRC_RENDER, SRC_POLICY, SRC_PPO, SRC_PPO_TRAIN, SRC_SNAPSHOT, SRC_ARS, SRC_MPC]
         if verbose:
             c.insert(1, "-Rpass-analysis=kernel-resource-usage")
             print(" ".join(c))

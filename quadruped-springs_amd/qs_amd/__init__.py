@@ -23,6 +23,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch / a GP
     if name == "DeviceARS":
         from .ars import DeviceARS
         return DeviceARS
+    if name == "DeviceMPC":
+        from .mpc import DeviceMPC
+        return DeviceMPC
     if name == "EnvSnapshot":
         from .snapshot import EnvSnapshot
         return EnvSnapshot

@@ -25,6 +25,7 @@ EXPORTS = (
     "qs_ars_create", "qs_ars_destroy", "qs_ars_set_stream", "qs_ars_perturb", "qs_ars_begin", "qs_ars_account", "qs_ars_alive", "qs_ars_returns",
     "qs_ars_finish", "qs_ars_get",
     "qs_step_masked", "qs_norm_step_masked",
+    "qs_mpc_create", "qs_mpc_destroy", "qs_mpc_set_stream", "qs_mpc_sample", "qs_mpc_feed", "qs_mpc_finish", "qs_mpc_get", "qs_mpc_set_plan",
 )
 
 
@@ -184,6 +185,16 @@ def load():
         lib.qs_ars_returns.argtypes = [vp, f32]
         lib.qs_ars_finish.argtypes = [vp, vp, vp, i32, f32, f32]
         lib.qs_ars_get.argtypes = [vp, i32, vp]
+    if hasattr(lib, "qs_mpc_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
+        lib.qs_mpc_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+        lib.qs_mpc_destroy.argtypes = [vp]
+        lib.qs_mpc_destroy.restype = None
+        lib.qs_mpc_set_stream.argtypes = [vp, vp]
+        lib.qs_mpc_sample.argtypes = [vp, vp, f32]
+        lib.qs_mpc_feed.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
+        lib.qs_mpc_finish.argtypes = [vp, i32, f32, vp]
+        lib.qs_mpc_get.argtypes = [vp, i32, vp]
+        lib.qs_mpc_set_plan.argtypes = [vp, vp, vp]
     lib.qs_last_error.restype = C.c_char_p
     lib.qs_version.restype = C.c_char_p
     # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)
