@@ -37,8 +37,12 @@ struct Moments { double n, mean, m2; };
 // took +55 us per step at N = 8192, `tools/time_vecnormalize.py`; a single kernel whose blocks wait for each other's moments was built and
 // measured in round 4: the device-scope fences of the hand-over write back and invalidate a whole L2 per XCD -- 120 us).  Every phase
 // issues all of a thread's loads before the first use (QN_CH at a time); a block's moments are plain sums about one of its own values (the
-// first row's: no cancellation, and adding needs no division); the blocks' moments are added up as sums about block 0's mean -- Chan's
-// pairwise merge (RunningMeanStd's own formula) written without its two divisions per pair.
+// first row's: no cancellation, and adding needs no division); the blocks' moments are added up as sums about the mean of the first block
+// that counted a row -- Chan's pairwise merge (RunningMeanStd's own formula) written without its two divisions per pair.  Without a mask
+// that block is block 0.  Under a mask a block may have counted nothing: it stores n = 0, mean = 0, m2 = 0 and adds nothing to the sums,
+// and its mean is no pivot (about 0 the merge cancels: a column at 1000 +- 0.01 loses ten of its sixteen digits of variance when rows
+// [0, 100) are frozen, the masked cases of tests/test_gpu_norm_shapes.py).  The search for that block runs under a mask only and is a chain of dependent loads, one per
+// leading empty block: up to n_parts of them when only the last rows are counted.
 #define QN_MAX_PARTS 512
 #ifndef QN_CH
 #define QN_CH 4
@@ -127,7 +131,13 @@ __global__ __launch_bounds__(256) void k_norm_finish(qs_norm_io io, double* __re
         const int c = c0 + cx, cc = c < C ? c : 0;
         const bool upd = training && c < C && ((c < o && with_obs) || (c == o && with_ret));
         if (training) {
-            const double P = part[cc].mean;        // sums about block 0's mean
+            // sums about the mean of the first block that counted a row: block 0's, unless a mask emptied it (its mean is then stored as 0, and
+            // about 0 a column at 1000 +- 0.01 loses ten digits of its variance).  Every block looks in the same order: the same P, the same bits.
+            // Without a mask every block counts its rows and nobody looks: the load below goes out with the loop's, as it always did.
+            Moments first = part[cc];
+            if (active != nullptr && upd)
+                for (int g = 1; first.n == 0.0 && g < n_parts; g++) first = part[(size_t)g * C + cc];
+            const double P = first.mean;
             double S0 = 0.0, S1 = 0.0, S2 = 0.0;
             for (int g0 = ry; g0 < n_parts; g0 += 8 * QN_MCH) {
                 Moments m[QN_MCH];
