@@ -4,8 +4,6 @@
 // kernel here is that header's functions, one lane per element, and nothing else.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include "qs_amd.h"
 #include "qs_ars.h"
 #include "qs_host.h"
@@ -101,13 +99,11 @@ __global__ __launch_bounds__(BLOCK) void k_ars_apply(float* __restrict__ theta, 
     if (i < n_params) theta[i] = ar::apply(theta[i], delta, n_params, i, idx, w, b, stats[1]);
 }
 
-unsigned blocks_of(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 int launch_returns(qs_ars* h, float alive_bonus_offset) {
     QS_HIP(hipMemsetAsync(h->steps, 0, sizeof(unsigned long long), h->stream));
     hipLaunchKernelGGL(k_ars_returns, dim3((unsigned)(2 * h->n_delta)), dim3(ar::WAVE), 0, h->stream, (const float*)h->ret, (const int*)h->len, h->m, alive_bonus_offset,
                        h->R, h->steps);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -121,69 +117,48 @@ void free_all(qs_ars* h) {
 extern "C" {
 
 int qs_ars_create(int n_envs, int n_delta, int n_params, int episodes_per_env, int device, qs_ars** out) {
-    if (!out) QS_FAIL(-1, "null argument");
     if (ar::check_shape(n_envs, n_delta, n_params, episodes_per_env, qs_g_err, sizeof(qs_g_err))) return -1;
-    if (int rc = qs_check_device(device)) return rc;
-    qs_ars* h = new (std::nothrow) qs_ars();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
+    qs_ars* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
     h->n_envs = n_envs; h->n_delta = n_delta; h->n_params = n_params; h->episodes_per_env = episodes_per_env;
-    h->m = ar::block_of(n_envs, n_delta); h->device = device;
-    DeviceGuard guard(device);
+    h->m = ar::block_of(n_envs, n_delta);
+    QS_ON_DEVICE(h);
     const size_t N = (size_t)n_envs, D = (size_t)n_delta;
-    hipError_t e = hipSuccess;
-    // (zeroed: a getter before the first begin / finish reads zeros, not what the allocator left)
-    auto zeroed = [&e](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-        if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-    };
-    zeroed((void**)&h->ret, N * sizeof(float)); zeroed((void**)&h->len, N * sizeof(int)); zeroed((void**)&h->episodes, N * sizeof(int));
-    zeroed((void**)&h->alive, N); zeroed((void**)&h->n_alive, sizeof(int)); zeroed((void**)&h->steps, sizeof(unsigned long long));
-    zeroed((void**)&h->R, 2 * D * sizeof(float)); zeroed((void**)&h->idx, D * sizeof(int)); zeroed((void**)&h->w, D * sizeof(float));
-    zeroed((void**)&h->stats, 2 * sizeof(float));
-    if (e != hipSuccess) {
-        snprintf(qs_g_err, sizeof(qs_g_err), "qs_ars_create: %d environments, %d directions: %s", n_envs, n_delta, hipGetErrorString(e));
-        free_all(h);
-        delete h;
-        return -2;
-    }
+    ZeroedAlloc zeroed;
+    zeroed(&h->ret, N); zeroed(&h->len, N); zeroed(&h->episodes, N); zeroed(&h->alive, N); zeroed(&h->n_alive, 1); zeroed(&h->steps, 1);
+    zeroed(&h->R, 2 * D); zeroed(&h->idx, D); zeroed(&h->w, D); zeroed(&h->stats, 2);
+    if (zeroed.failed("qs_ars_create: %d environments, %d directions", n_envs, n_delta)) { qs_ars_destroy(h); return -2; }
     *out = h;
     return 0;
 }
 
-void qs_ars_destroy(qs_ars* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    free_all(h);
-    delete h;
-}
+void qs_ars_destroy(qs_ars* h) { qs_delete_handle(h, free_all); }
 
-int qs_ars_set_stream(qs_ars* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_ars_set_stream(qs_ars* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_ars_perturb(qs_ars* h, const float* theta, const float* delta, float sigma, float* candidates) {
     if (!h || !theta || !delta || !candidates) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    hipLaunchKernelGGL(k_ars_perturb, dim3(blocks_of((long long)h->n_delta * h->n_params)), dim3(BLOCK), 0, h->stream, theta, delta, h->n_delta, h->n_params, sigma,
+    hipLaunchKernelGGL(k_ars_perturb, dim3(qs_blocks((long long)h->n_delta * h->n_params, BLOCK)), dim3(BLOCK), 0, h->stream, theta, delta, h->n_delta, h->n_params, sigma,
                        candidates);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
 int qs_ars_begin(qs_ars* h) {
     if (!h) QS_FAIL(-1, "null handle");
     QS_ON_DEVICE(h);
-    hipLaunchKernelGGL(k_ars_begin, dim3(blocks_of(h->n_envs)), dim3(BLOCK), 0, h->stream, h->ret, h->len, h->episodes, h->alive, h->n_envs, h->n_alive, h->steps);
-    QS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ars_begin, dim3(qs_blocks(h->n_envs, BLOCK)), dim3(BLOCK), 0, h->stream, h->ret, h->len, h->episodes, h->alive, h->n_envs, h->n_alive, h->steps);
+    QS_LAUNCHED();
     return 0;
 }
 
 int qs_ars_account(qs_ars* h, const float* raw_reward, const uint8_t* done) {
     if (!h || !raw_reward || !done) QS_FAIL(-1, "null argument");
     QS_ON_DEVICE(h);
-    hipLaunchKernelGGL(k_ars_account, dim3(blocks_of(h->n_envs)), dim3(BLOCK), 0, h->stream, h->ret, h->len, h->episodes, h->alive, raw_reward, done, h->n_envs,
+    hipLaunchKernelGGL(k_ars_account, dim3(qs_blocks(h->n_envs, BLOCK)), dim3(BLOCK), 0, h->stream, h->ret, h->len, h->episodes, h->alive, raw_reward, done, h->n_envs,
                        h->episodes_per_env, h->n_alive);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -208,34 +183,31 @@ int qs_ars_finish(qs_ars* h, float* theta, const float* delta, int n_top, float 
     if (int rc = launch_returns(h, alive_bonus_offset)) return rc;
     hipLaunchKernelGGL(k_ars_select, dim3(1), dim3((unsigned)((h->n_delta + ar::WAVE - 1) / ar::WAVE * ar::WAVE)), 0, h->stream, (const float*)h->R, h->n_delta, n_top,
                        learning_rate, h->idx, h->w, h->stats);
-    QS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ars_apply, dim3(blocks_of(h->n_params)), dim3(BLOCK), 0, h->stream, theta, delta, h->n_params, (const int*)h->idx, (const float*)h->w, n_top,
+    QS_LAUNCHED();
+    hipLaunchKernelGGL(k_ars_apply, dim3(qs_blocks(h->n_params, BLOCK)), dim3(BLOCK), 0, h->stream, theta, delta, h->n_params, (const int*)h->idx, (const float*)h->w, n_top,
                        (const float*)h->stats);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
 int qs_ars_get(qs_ars* h, int what, void* dev_out) {
     if (!h || !dev_out) QS_FAIL(-1, "null argument");
     const size_t N = (size_t)h->n_envs, D = (size_t)h->n_delta;
-    const void* src = nullptr;
-    size_t bytes = 0;
+    QsSpan s;
     switch (what) {
-        case QS_ARS_GET_RET: src = h->ret; bytes = N * sizeof(float); break;
-        case QS_ARS_GET_LEN: src = h->len; bytes = N * sizeof(int); break;
-        case QS_ARS_GET_EPISODES: src = h->episodes; bytes = N * sizeof(int); break;
-        case QS_ARS_GET_ALIVE: src = h->alive; bytes = N; break;
-        case QS_ARS_GET_N_ALIVE: src = h->n_alive; bytes = sizeof(int); break;
-        case QS_ARS_GET_STEPS: src = h->steps; bytes = sizeof(unsigned long long); break;
-        case QS_ARS_GET_RETURNS: src = h->R; bytes = 2 * D * sizeof(float); break;
-        case QS_ARS_GET_IDX: src = h->idx; bytes = D * sizeof(int); break;
-        case QS_ARS_GET_W: src = h->w; bytes = D * sizeof(float); break;
-        case QS_ARS_GET_STATS: src = h->stats; bytes = 2 * sizeof(float); break;
+        case QS_ARS_GET_RET: s = {h->ret, N * sizeof(float)}; break;
+        case QS_ARS_GET_LEN: s = {h->len, N * sizeof(int)}; break;
+        case QS_ARS_GET_EPISODES: s = {h->episodes, N * sizeof(int)}; break;
+        case QS_ARS_GET_ALIVE: s = {h->alive, N}; break;
+        case QS_ARS_GET_N_ALIVE: s = {h->n_alive, sizeof(int)}; break;
+        case QS_ARS_GET_STEPS: s = {h->steps, sizeof(unsigned long long)}; break;
+        case QS_ARS_GET_RETURNS: s = {h->R, 2 * D * sizeof(float)}; break;
+        case QS_ARS_GET_IDX: s = {h->idx, D * sizeof(int)}; break;
+        case QS_ARS_GET_W: s = {h->w, D * sizeof(float)}; break;
+        case QS_ARS_GET_STATS: s = {h->stats, 2 * sizeof(float)}; break;
         default: QS_FAIL(-1, "qs_ars_get: what = %d is no QS_ARS_GET_*", what);
     }
-    QS_ON_DEVICE(h);
-    QS_HIP(hipMemcpyAsync(dev_out, src, bytes, hipMemcpyDeviceToDevice, h->stream));
-    return 0;
+    return qs_copy_out(h, s, dev_out);
 }
 
 }  // extern "C"

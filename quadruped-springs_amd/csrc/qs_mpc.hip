@@ -4,8 +4,6 @@
 // arithmetic and its order are csrc/qs_mpc.h; every kernel here is that header's functions and nothing else.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include "qs_amd.h"
 #include "qs_mpc.h"
 #include "qs_host.h"
@@ -122,8 +120,6 @@ __global__ __launch_bounds__(BLOCK) void k_mpc_set_plan(float* __restrict__ plan
     plan[at] = src ? src[at] : 0.0f;
 }
 
-unsigned blocks_of(long long n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 void free_all(qs_mpc* h) {
     hipFree(h->plan); hipFree(h->seq); hipFree(h->score); hipFree(h->running); hipFree(h->best); hipFree(h->best_score);
 }
@@ -133,51 +129,31 @@ void free_all(qs_mpc* h) {
 extern "C" {
 
 int qs_mpc_create(int n_robots, int n_candidates, int horizon, int action_dim, int device, qs_mpc** out) {
-    if (!out) QS_FAIL(-1, "null argument");
     if (mp::check_shape(n_robots, n_candidates, horizon, action_dim, qs_g_err, sizeof(qs_g_err))) return -1;
-    if (int rc = qs_check_device(device)) return rc;
-    qs_mpc* h = new (std::nothrow) qs_mpc();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
-    h->M = n_robots; h->C = n_candidates; h->H = horizon; h->d = action_dim; h->device = device;
-    DeviceGuard guard(device);
+    qs_mpc* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
+    h->M = n_robots; h->C = n_candidates; h->H = horizon; h->d = action_dim;
+    QS_ON_DEVICE(h);
     const size_t M = (size_t)n_robots, MC = M * n_candidates, Hd = (size_t)horizon * action_dim;
-    hipError_t e = hipSuccess;
-    // (zeroed: the first plan is zero, and a getter before the first sample reads zeros)
-    auto zeroed = [&e](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
-        if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-    };
-    zeroed((void**)&h->plan, M * Hd * sizeof(float)); zeroed((void**)&h->seq, MC * Hd * sizeof(float)); zeroed((void**)&h->score, MC * sizeof(float));
-    zeroed((void**)&h->running, MC); zeroed((void**)&h->best, M * sizeof(int)); zeroed((void**)&h->best_score, M * sizeof(float));
-    if (e != hipSuccess) {
-        snprintf(qs_g_err, sizeof(qs_g_err), "qs_mpc_create: %d robots x %d candidates x horizon %d: %s", n_robots, n_candidates, horizon, hipGetErrorString(e));
-        free_all(h);
-        delete h;
-        return -2;
-    }
+    ZeroedAlloc zeroed;                                                        // (the first plan is zero)
+    zeroed(&h->plan, M * Hd); zeroed(&h->seq, MC * Hd); zeroed(&h->score, MC); zeroed(&h->running, MC); zeroed(&h->best, M); zeroed(&h->best_score, M);
+    if (zeroed.failed("qs_mpc_create: %d robots x %d candidates x horizon %d", n_robots, n_candidates, horizon)) { qs_mpc_destroy(h); return -2; }
     *out = h;
     return 0;
 }
 
-void qs_mpc_destroy(qs_mpc* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    free_all(h);
-    delete h;
-}
+void qs_mpc_destroy(qs_mpc* h) { qs_delete_handle(h, free_all); }
 
-int qs_mpc_set_stream(qs_mpc* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_mpc_set_stream(qs_mpc* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_mpc_sample(qs_mpc* h, const float* eps, float sigma) {
     if (!h || !eps) QS_FAIL(-1, "null argument");
     if (mp::check_sigma(sigma, qs_g_err, sizeof(qs_g_err))) return -1;
     QS_ON_DEVICE(h);
     const int MC = h->M * h->C;
-    hipLaunchKernelGGL(k_mpc_sample, dim3(blocks_of((long long)h->H * MC * h->d)), dim3(BLOCK), 0, h->stream, (const float*)h->plan, eps, MC, h->C, h->H, h->d, sigma,
+    hipLaunchKernelGGL(k_mpc_sample, dim3(qs_blocks((long long)h->H * MC * h->d, BLOCK)), dim3(BLOCK), 0, h->stream, (const float*)h->plan, eps, MC, h->C, h->H, h->d, sigma,
                        h->seq, h->score, h->running);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -188,9 +164,9 @@ int qs_mpc_feed(qs_mpc* h, int step, const float* reward, const uint8_t* done, c
     if (step == h->H && (!reward_end || reward_end_stride < 1)) QS_FAIL(-1, "qs_mpc_feed: step = horizon needs reward_end and a positive row stride");
     QS_ON_DEVICE(h);
     const int MC = h->M * h->C;
-    hipLaunchKernelGGL(k_mpc_feed, dim3(blocks_of((long long)MC * h->d)), dim3(BLOCK), 0, h->stream, step, (const float*)h->seq, h->score, h->running, h->M, MC, h->H,
+    hipLaunchKernelGGL(k_mpc_feed, dim3(qs_blocks((long long)MC * h->d, BLOCK)), dim3(BLOCK), 0, h->stream, step, (const float*)h->seq, h->score, h->running, h->M, MC, h->H,
                        h->d, reward, done, reward_end, reward_end_stride, actions, active);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -202,7 +178,7 @@ int qs_mpc_finish(qs_mpc* h, int method, float lambda, float* actions) {
     const unsigned lanes = (unsigned)((h->H * h->d + mp::WAVE - 1) / mp::WAVE * mp::WAVE);
     hipLaunchKernelGGL(k_mpc_finish, dim3((unsigned)h->M), dim3(lanes), 0, h->stream, (const float*)h->seq, (const float*)h->score, h->M * h->C, h->C, h->H, h->d, method,
                        lambda, h->plan, actions, h->best, h->best_score);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -210,28 +186,25 @@ int qs_mpc_set_plan(qs_mpc* h, const float* plan, const uint8_t* mask) {
     if (!h) QS_FAIL(-1, "null handle");
     QS_ON_DEVICE(h);
     const int Hd = h->H * h->d;
-    hipLaunchKernelGGL(k_mpc_set_plan, dim3(blocks_of((long long)h->M * Hd)), dim3(BLOCK), 0, h->stream, h->plan, plan, mask, h->M, Hd);
-    QS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_mpc_set_plan, dim3(qs_blocks((long long)h->M * Hd, BLOCK)), dim3(BLOCK), 0, h->stream, h->plan, plan, mask, h->M, Hd);
+    QS_LAUNCHED();
     return 0;
 }
 
 int qs_mpc_get(qs_mpc* h, int what, void* dev_out) {
     if (!h || !dev_out) QS_FAIL(-1, "null argument");
     const size_t M = (size_t)h->M, MC = M * h->C, Hd = (size_t)h->H * h->d;
-    const void* src = nullptr;
-    size_t bytes = 0;
+    QsSpan s;
     switch (what) {
-        case QS_MPC_GET_PLAN: src = h->plan; bytes = M * Hd * sizeof(float); break;
-        case QS_MPC_GET_SEQ: src = h->seq; bytes = MC * Hd * sizeof(float); break;
-        case QS_MPC_GET_SCORE: src = h->score; bytes = MC * sizeof(float); break;
-        case QS_MPC_GET_RUNNING: src = h->running; bytes = MC; break;
-        case QS_MPC_GET_BEST: src = h->best; bytes = M * sizeof(int); break;
-        case QS_MPC_GET_BEST_SCORE: src = h->best_score; bytes = M * sizeof(float); break;
+        case QS_MPC_GET_PLAN: s = {h->plan, M * Hd * sizeof(float)}; break;
+        case QS_MPC_GET_SEQ: s = {h->seq, MC * Hd * sizeof(float)}; break;
+        case QS_MPC_GET_SCORE: s = {h->score, MC * sizeof(float)}; break;
+        case QS_MPC_GET_RUNNING: s = {h->running, MC}; break;
+        case QS_MPC_GET_BEST: s = {h->best, M * sizeof(int)}; break;
+        case QS_MPC_GET_BEST_SCORE: s = {h->best_score, M * sizeof(float)}; break;
         default: QS_FAIL(-1, "qs_mpc_get: what = %d is no QS_MPC_GET_*", what);
     }
-    QS_ON_DEVICE(h);
-    QS_HIP(hipMemcpyAsync(dev_out, src, bytes, hipMemcpyDeviceToDevice, h->stream));
-    return 0;
+    return qs_copy_out(h, s, dev_out);
 }
 
 }  // extern "C"

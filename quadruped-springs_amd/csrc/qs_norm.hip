@@ -11,7 +11,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include "qs_amd.h"
 #include "qs_host.h"
 
@@ -24,7 +23,7 @@ struct qs_norm {
     // block of k_norm_finish works out the new statistics from the old ones; block 0 stores them where no block reads), then `cur` flips.
     double* d_stat;
     int cur;
-    void* d_part;    // per-block moments of the batch [n_parts][C] (k_norm_moments -> k_norm_finish)
+    double* d_part;  // per-block moments of the batch [n_parts][C] (Moments = 3 doubles; k_norm_moments -> k_norm_finish)
     int n_parts, rows_per_block;
     double* d_ret;   // discounted return of every environment (VecNormalize.returns)
 };
@@ -234,41 +233,32 @@ extern "C" {
 
 int qs_norm_create(int n_envs, int obs_dim, double clip_obs, double clip_reward, double gamma, double epsilon, int device, qs_norm** out) {
     if (!out || n_envs <= 0 || obs_dim <= 0 || obs_dim > 255) QS_FAIL(-1, "bad argument (n_envs %d, obs_dim %d)", n_envs, obs_dim);
-    if (int rc = qs_check_device(device)) return rc;
-    DeviceGuard guard(device);
-    qs_norm* h = new (std::nothrow) qs_norm();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
-    h->n = n_envs; h->o = obs_dim; h->device = device; h->clip_obs = clip_obs; h->clip_rew = clip_reward; h->gamma = gamma; h->eps = epsilon;
+    qs_norm* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
+    QS_ON_DEVICE(h);
+    h->n = n_envs; h->o = obs_dim; h->clip_obs = clip_obs; h->clip_rew = clip_reward; h->gamma = gamma; h->eps = epsilon;
     const int C = obs_dim + 1, S = 5 * C + 2;
-#define QN_HIP_H(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(qs_g_err, sizeof(qs_g_err), "%s failed: %s", #call, hipGetErrorString(e_)); qs_norm_destroy(h); return -2; } } while (0)
-    QN_HIP_H(hipMalloc(&h->d_stat, (size_t)2 * S * sizeof(double)));
     // rows per block: 64 (128 blocks at N = 8192: eight rows per thread and column, sixteen blocks' moments per thread in k_norm_finish),
     // never more than QN_MAX_PARTS blocks
     h->rows_per_block = ((n_envs + QN_MAX_PARTS - 1) / QN_MAX_PARTS + 7) / 8 * 8;
     if (h->rows_per_block < 64) h->rows_per_block = 64;
     h->n_parts = (n_envs + h->rows_per_block - 1) / h->rows_per_block;
-    QN_HIP_H(hipMalloc(&h->d_part, (size_t)h->n_parts * C * 3 * sizeof(double)));
-    QN_HIP_H(hipMalloc(&h->d_ret, (size_t)n_envs * sizeof(double)));
-    QN_HIP_H(hipMemset(h->d_ret, 0, (size_t)n_envs * sizeof(double)));
+    ZeroedAlloc zeroed;
+    zeroed(&h->d_stat, (size_t)2 * S); zeroed(&h->d_part, (size_t)h->n_parts * C * 3); zeroed(&h->d_ret, (size_t)n_envs);
     double init[5 * 256 + 2];
     for (int c = 0; c < C; c++) { init[c] = 0.0; init[C + c] = 1.0; init[2 * C + 2 + c] = 0.0; init[3 * C + 2 + c] = 0.0; init[4 * C + 2 + c] = 1.0 / sqrt(1.0 + (double)epsilon); }
     init[2 * C] = init[2 * C + 1] = 1e-4;   // RunningMeanStd(epsilon=1e-4)
-    for (int k = 0; k < 2; k++) QN_HIP_H(hipMemcpy(QN_STAT(h, k), init, (size_t)S * sizeof(double), hipMemcpyHostToDevice));
-#undef QN_HIP_H
+    for (int k = 0; k < 2; k++) if (zeroed.e == hipSuccess) zeroed.e = hipMemcpy(QN_STAT(h, k), init, (size_t)S * sizeof(double), hipMemcpyHostToDevice);
+    if (zeroed.failed("qs_norm_create: %d environments x %d observations", n_envs, obs_dim)) { qs_norm_destroy(h); return -2; }
     *out = h;
     return 0;
 }
 
 void qs_norm_destroy(qs_norm* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    hipFree(h->d_stat); hipFree(h->d_ret); hipFree(h->d_part);
-    delete h;
+    qs_delete_handle(h, [](qs_norm* h) { hipFree(h->d_stat); hipFree(h->d_ret); hipFree(h->d_part); });
 }
 
-int qs_norm_set_stream(qs_norm* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_norm_set_stream(qs_norm* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_norm_set_stats(qs_norm* h, const double* obs_mean, const double* obs_var, double obs_count, double ret_mean, double ret_var, double ret_count) {
     if (!h || !obs_mean || !obs_var) QS_FAIL(-1, "null argument");
@@ -308,7 +298,7 @@ static int norm_launch(qs_norm* h, const qs_norm_io& io, int training, int with_
     hipLaunchKernelGGL(k_norm_finish, dim3(h->n_parts), dim3(256), 0, h->stream, io, h->d_ret, h->n, h->o, QN_STAT(h, h->cur), QN_STAT(h, h->cur ^ 1),
                        (const Moments*)h->d_part, h->n_parts, h->rows_per_block, (double)h->n, h->eps, h->clip_obs, h->clip_rew,
                        training, with_obs, with_ret, norm_obs, norm_reward, active);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     if (training) h->cur ^= 1;
     return 0;
 }

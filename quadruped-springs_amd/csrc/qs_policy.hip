@@ -11,8 +11,6 @@
 // past the end of a policy's block are masked lanes (zero observation, no store): tiles never straddle two policies.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
-#include <new>
 #include "qs_policy.h"
 #include "qs_host.h"
 
@@ -133,11 +131,9 @@ int qs_policy_create(const qs_policy_desc* d, int device, qs_policy** out) {
     if (!d || !out) QS_FAIL(-1, "null argument");
     Net net;
     if (net_from_desc(*d, net, qs_g_err, sizeof(qs_g_err))) return -1;
-    if (int rc = qs_check_device(device)) return rc;
-    qs_policy* h = new (std::nothrow) qs_policy();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
-    h->desc = *d; h->net = net; h->device = device;
+    qs_policy* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
+    h->desc = *d; h->net = net;
     h->n_per = d->n_envs / d->n_policies;
     h->tiles_per_policy = (h->n_per + TILE - 1) / TILE;
     const Net* nets[1] = {&h->net};
@@ -147,21 +143,16 @@ int qs_policy_create(const qs_policy_desc* d, int device, qs_policy** out) {
     h->wg_per_policy = (h->tiles_per_policy + h->waves - 1) / h->waves;
     h->lds_bytes = lds_bytes(h->w_floats, h->waves, 1, h->act_stride);
     h->kernel = wide ? k_policy<16> : k_policy<4>;
-    DeviceGuard guard(device);
+    QS_ON_DEVICE(h);
     hipError_t e = hipFuncSetAttribute((const void*)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) { snprintf(qs_g_err, sizeof(qs_g_err), "hipFuncSetAttribute(%zu bytes of LDS) failed: %s", h->lds_bytes, hipGetErrorString(e)); delete h; return -2; }
     *out = h;
     return 0;
 }
 
-void qs_policy_destroy(qs_policy* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    delete h;
-}
+void qs_policy_destroy(qs_policy* h) { qs_delete_handle(h, [](qs_policy*) {}); }   // (no device memory of its own)
 
-int qs_policy_set_stream(qs_policy* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_policy_set_stream(qs_policy* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_policy_param_count(const qs_policy* h) { if (!h) QS_FAIL(-1, "null handle"); return h->net.n_params; }
 
@@ -182,7 +173,7 @@ int qs_policy_act(qs_policy* h, const float* obs, const float* eps, const float*
     a.n_per = h->n_per; a.tiles_per_policy = h->tiles_per_policy; a.wg_per_policy = h->wg_per_policy; a.act_stride = h->act_stride; a.w_floats = h->w_floats;
     const dim3 grid((unsigned)(h->desc.n_policies * h->wg_per_policy)), block(64 * h->waves);
     hipLaunchKernelGGL(h->kernel, grid, block, h->lds_bytes, h->stream, h->net, a);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 

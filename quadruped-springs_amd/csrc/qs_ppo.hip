@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include "qs_ppo.h"
 #include "qs_host.h"
 
@@ -189,7 +188,7 @@ int launch(qs_ac* h, AcKernel kernel, const AcArgs& a, bool one_wave) {
     const size_t lds = one_wave ? h->lds_bytes_one : h->lds_bytes;
     const dim3 grid((unsigned)((h->tiles + waves - 1) / waves)), block(64 * waves);
     hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, h->actor, h->critic, a);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -211,11 +210,9 @@ int qs_ac_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int 
     if (net_from_desc(*actor, na, qs_g_err, sizeof(qs_g_err))) return -1;
     if (net_from_desc(*critic, nc, qs_g_err, sizeof(qs_g_err))) return -1;
     if (ppo::check_pair(*actor, *critic, qs_g_err, sizeof(qs_g_err))) return -1;
-    if (int rc = qs_check_device(device)) return rc;
-    qs_ac* h = new (std::nothrow) qs_ac();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
-    h->actor_desc = *actor; h->critic_desc = *critic; h->actor = na; h->critic = nc; h->device = device;
+    qs_ac* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
+    h->actor_desc = *actor; h->critic_desc = *critic; h->actor = na; h->critic = nc;
     h->n = actor->n_envs;
     h->tiles = (h->n + TILE - 1) / TILE;
     const Net* nets[2] = {&h->actor, &h->critic};
@@ -225,7 +222,7 @@ int qs_ac_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int 
     h->lds_bytes = lds_bytes(h->w_floats, h->waves, 2, h->act_stride); h->lds_bytes_one = lds_bytes(h->w_floats, 1, 2, h->act_stride);
     h->k_collect = wide ? k_actor_critic<16, true> : k_actor_critic<4, true>;
     h->k_critic = wide ? k_actor_critic<16, false> : k_actor_critic<4, false>;
-    DeviceGuard guard(device);
+    QS_ON_DEVICE(h);
     const int lds = (int)h->lds_bytes;            // (the largest launch; a one-wave launch needs less)
     hipError_t e = hipFuncSetAttribute((const void*)h->k_collect, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)h->k_critic, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -234,14 +231,9 @@ int qs_ac_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int 
     return 0;
 }
 
-void qs_ac_destroy(qs_ac* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    delete h;
-}
+void qs_ac_destroy(qs_ac* h) { qs_delete_handle(h, [](qs_ac*) {}); }   // (no device memory of its own)
 
-int qs_ac_set_stream(qs_ac* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_ac_set_stream(qs_ac* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_ac_set_params(qs_ac* h, const float* actor_params, const float* critic_params) {
     if (!h || !actor_params || !critic_params) QS_FAIL(-1, "null argument");
@@ -283,9 +275,9 @@ int qs_gae(const float* rewards, const float* values, const float* episode_start
            float gamma, float lambda, float* advantages, float* returns, void* hip_stream) {
     if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns) QS_FAIL(-1, "null argument");
     if (T <= 0 || N <= 0) QS_FAIL(-1, "qs_gae: T = %d and N = %d must be positive", T, N);
-    hipLaunchKernelGGL(k_gae, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, rewards, values, episode_starts, last_values,
+    hipLaunchKernelGGL(k_gae, dim3(qs_blocks(N, 256)), dim3(256), 0, (hipStream_t)hip_stream, rewards, values, episode_starts, last_values,
                        last_dones, T, N, gamma, lambda, advantages, returns);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 

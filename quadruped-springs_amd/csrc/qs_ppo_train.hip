@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include "qs_ppo_train.h"
 #include "qs_host.h"
 
@@ -383,42 +382,26 @@ int qs_ppo_create(const qs_policy_desc* actor, const qs_policy_desc* critic, int
     if (waves == 0)
         QS_FAIL(-1, "qs_ppo_create: the weight images (%d floats) and one wave's rows need %zu bytes of LDS, a compute unit has %zu", image_floats,
                 tr::lds_bytes(image_floats, 1), LDS_MAX_BYTES);
-    if (int rc = qs_check_device(device)) return rc;
-    qs_ppo* h = new (std::nothrow) qs_ppo();
-    if (!h) QS_FAIL(-4, "out of host memory");
-    memset(h, 0, sizeof(*h));
-    h->actor = na; h->critic = nc; h->ia = ia; h->ic = ic; h->device = device; h->max_batch = max_batch;
+    qs_ppo* h;
+    if (int rc = qs_new_handle(out, device, &h)) return rc;
+    h->actor = na; h->critic = nc; h->ia = ia; h->ic = ic; h->max_batch = max_batch;
     h->n_total = tr::total_params(na, nc); h->stride = tr::part_stride(h->n_total);
     h->waves = waves; h->image_floats = image_floats; h->lds_bytes = tr::lds_bytes(image_floats, waves);
-    DeviceGuard guard(device);
-    hipError_t e = hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    const size_t parts_bytes = (size_t)tr::PARTS * h->stride * sizeof(float);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->parts, parts_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->moments, 2 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sumsq, (size_t)tr::norm_blocks(h->n_total) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->refused, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(h->refused, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(h->parts, 0, parts_bytes);                  // (a row's pad and spare statistics are never written)
-    if (e == hipSuccess) e = hipMemset(h->sumsq, 0, (size_t)tr::norm_blocks(h->n_total) * sizeof(float));
-    if (e != hipSuccess) {
-        snprintf(qs_g_err, sizeof(qs_g_err), "qs_ppo_create: %zu bytes of LDS, %zu bytes of part rows: %s", h->lds_bytes, parts_bytes, hipGetErrorString(e));
-        hipFree(h->parts); hipFree(h->moments); hipFree(h->sumsq); hipFree(h->refused);
-        delete h;
-        return -2;
-    }
+    QS_ON_DEVICE(h);
+    ZeroedAlloc zeroed;
+    zeroed.e = hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+    const size_t parts_floats = (size_t)tr::PARTS * h->stride;                     // (a row's pad and spare statistics are never written)
+    zeroed(&h->parts, parts_floats); zeroed(&h->moments, 2); zeroed(&h->sumsq, (size_t)tr::norm_blocks(h->n_total)); zeroed(&h->refused, 1);
+    if (zeroed.failed("qs_ppo_create: %zu bytes of LDS, %zu bytes of part rows", h->lds_bytes, parts_floats * sizeof(float))) { qs_ppo_destroy(h); return -2; }
     *out = h;
     return 0;
 }
 
 void qs_ppo_destroy(qs_ppo* h) {
-    if (!h) return;
-    QS_ON_DEVICE(h);
-    hipStreamSynchronize(h->stream);
-    hipFree(h->parts); hipFree(h->moments); hipFree(h->sumsq); hipFree(h->refused);
-    delete h;
+    qs_delete_handle(h, [](qs_ppo* h) { hipFree(h->parts); hipFree(h->moments); hipFree(h->sumsq); hipFree(h->refused); });
 }
 
-int qs_ppo_set_stream(qs_ppo* h, void* s) { if (!h) QS_FAIL(-1, "null handle"); h->stream = (hipStream_t)s; return 0; }
+int qs_ppo_set_stream(qs_ppo* h, void* s) { return qs_set_stream_of(h, s); }
 
 int qs_ppo_bind(qs_ppo* h, float* actor_params, float* critic_params, float* log_std, float* exp_avg, float* exp_avg_sq) {
     if (!h || !actor_params || !critic_params || !log_std || !exp_avg || !exp_avg_sq) QS_FAIL(-1, "null argument");
@@ -442,15 +425,15 @@ int qs_ppo_grad(qs_ppo* h, const float* observations, const float* actions, cons
     a.clip_range = hyper->clip_range; a.vf_coef = hyper->vf_coef; a.ia = h->ia; a.ic = h->ic;
     if (a.norm_on) {
         hipLaunchKernelGGL(k_adv_moments, dim3(1), dim3(tr::MOM_CHAINS), 0, h->stream, advantages, indices, total, batch, h->moments);
-        QS_HIP(hipGetLastError());
+        QS_LAUNCHED();
     }
     const int used = tr::parts_used(batch);
     hipLaunchKernelGGL(k_ppo_grad, dim3((unsigned)((used + h->waves - 1) / h->waves)), dim3(64 * h->waves), h->lds_bytes, h->stream, h->actor, h->critic, a);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)tr::norm_blocks(h->n_total)), dim3(tr::NORM_BLOCK), 0, h->stream, (const float*)h->parts, h->stride, h->n_total,
                        h->actor.n_params + h->critic.n_params, h->actor.action_dim, batch, (const float*)h->log_std, hyper->ent_coef, hyper->vf_coef, grad_out,
                        h->sumsq, stats_out, h->refused);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 
@@ -461,7 +444,7 @@ int qs_ppo_adam(qs_ppo* h, const float* grad, const qs_ppo_hyper* hyper, int ste
     QS_ON_DEVICE(h);
     hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, h->stream, grad, (const float*)h->sumsq, tr::norm_blocks(h->n_total), h->actor.n_params,
                        h->critic.n_params, h->n_total, tr::adam_consts(*hyper, step), h->pa, h->pc, h->log_std, h->m, h->v, stats_inout);
-    QS_HIP(hipGetLastError());
+    QS_LAUNCHED();
     return 0;
 }
 

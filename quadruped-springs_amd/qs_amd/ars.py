@@ -15,36 +15,17 @@ unspecified), and an environment still running at `horizon` contributes what it 
 import ctypes as C
 
 from . import lib as _lib
+from .handle import DeviceHandle, auto_reset_of, ptr, raw_reward_of, takes_active
 
 MAX_DELTA = 1024      # csrc/qs_ars.h: the selection is one workgroup
 GET = dict(ret=0, len=1, episodes=2, alive=3, n_alive=4, steps=5, returns=6, idx=7, w=8, stats=9)   # QS_ARS_GET_*
 
 
-def _auto_reset_of(env):
-    """True / False where the environment (or what it wraps) says, None where it does not"""
-    e = env
-    while e is not None:
-        if hasattr(e, "auto_reset"):
-            return bool(e.auto_reset)
-        if hasattr(e, "cfg") and hasattr(e.cfg, "auto_reset"):
-            return bool(e.cfg.auto_reset)
-        e = getattr(e, "venv", None)
-    return None
-
-
-def _takes_active(env):
-    """whether env.step_tensor has the active= keyword (QuadrupedVecEnv, DeviceVecNormalize)"""
-    import inspect
-    try:
-        return "active" in inspect.signature(env.step_tensor).parameters
-    except (AttributeError, TypeError, ValueError):
-        return False
-
-
-class DeviceARS:
+class DeviceARS(DeviceHandle):
     """ARS over a QuadrupedVecEnv or a DeviceVecNormalize around one.  `policy` is a DevicePolicy(num_envs=N, n_policies=2 n_delta) (anything
     with n_params, n_policies, num_envs, device and set_params).  env may be None for a learner that is only handed rewards and dones
     (begin / account / finish)."""
+    _prefix, _owner = "qs_ars", "learner"
 
     def __init__(self, env, policy, n_delta=8, n_top=None, learning_rate=0.02, delta_std=0.05, zero_policy=True, alive_bonus_offset=0.0,
                  episodes_per_env=1, horizon=300, check_every=16, seed=0, freeze_done=False):
@@ -75,12 +56,12 @@ class DeviceARS:
         if env is not None:
             if int(env.num_envs) != self.num_envs:
                 raise ValueError(f"the environment has num_envs = {env.num_envs}, the policy {self.num_envs}")
-            if self.episodes_per_env > 1 and _auto_reset_of(env) is not True:
+            if self.episodes_per_env > 1 and auto_reset_of(env) is not True:
                 raise ValueError(f"episodes_per_env = {self.episodes_per_env} needs an environment with auto_reset=True (an environment that is not reset "
                                  "has no second episode)")
         self.learning_rate, self.delta_std, self.alive_bonus_offset = float(learning_rate), float(delta_std), float(alive_bonus_offset)
         self.freeze_done = bool(freeze_done)
-        if self.freeze_done and env is not None and not _takes_active(env):
+        if self.freeze_done and env is not None and not takes_active(env):
             raise ValueError(f"freeze_done=True needs an environment whose step_tensor takes active= ({type(env).__name__}.step_tensor does not)")
         self.device = policy.device
         if self.device.type != "cuda":
@@ -105,36 +86,15 @@ class DeviceARS:
                          alive=torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device), n_alive=torch.zeros(1, **i32),
                          steps=torch.zeros(1, dtype=torch.int64, device=self.device), returns=torch.zeros(P, **f32), idx=torch.zeros(self.n_delta, **i32),
                          w=torch.zeros(self.n_delta, **f32), stats=torch.zeros(2, **f32))
-        self._normalised = env is not None and hasattr(env, "venv") and hasattr(env, "old_reward")
         self.delta = None
         self.num_timesteps = 0
         self.iteration = 0
         self.last_rollout_steps = 0
 
-    # ---- plumbing
-    def _stream(self):
-        _lib.check(self.lib.qs_ars_set_stream(self.h, C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
-
-    def _check(self, name, x, shape, dtype):
-        t = self.torch
-        if not t.is_tensor(x):
-            raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-        if x.dtype != dtype:
-            raise ValueError(f"{name} must be {dtype}, got {x.dtype}")
-        if x.device != self.device:
-            raise ValueError(f"{name} is on {x.device}, this learner on {self.device}")
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {tuple(shape)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        return C.c_void_p(x.data_ptr())
-
     def get(self, what):
         """a device tensor with the handle's `what` (one of GET; a reused buffer, a stream-ordered copy): ret, len, episodes, alive [N];
         n_alive, steps [1]; returns [2 n_delta]; idx, w [n_top] of the last finish; stats [2] = std, step"""
-        out = self._out[what]
-        self._stream()
-        _lib.check(self.lib.qs_ars_get(self.h, GET[what], C.c_void_p(out.data_ptr())))
+        out = self._get(what, GET, self._out)
         return out[:self.n_top] if what in ("idx", "w") else out
 
     # ---- the steps of an iteration (csrc/qs_ars.h 1-6)
@@ -144,9 +104,9 @@ class DeviceARS:
 
     def perturb(self, delta):
         """candidates = theta +- delta_std * delta, written into the tensor the policy reads; delta is kept for finish()"""
-        p = self._check("delta", delta, (self.n_delta, self.n_params), self.torch.float32)
+        p = self._arg("delta", delta, (self.n_delta, self.n_params))
         self._stream()
-        _lib.check(self.lib.qs_ars_perturb(self.h, C.c_void_p(self.theta.data_ptr()), p, self.delta_std, C.c_void_p(self.candidates.data_ptr())))
+        _lib.check(self.lib.qs_ars_perturb(self.h, ptr(self.theta), p, self.delta_std, ptr(self.candidates)))
         self.delta = delta
         return self.candidates
 
@@ -156,8 +116,7 @@ class DeviceARS:
 
     def account(self, raw_reward, done):
         """one environment step: raw_reward float32 [N], done uint8 [N]"""
-        t = self.torch
-        pr, pd = self._check("raw_reward", raw_reward, (self.num_envs,), t.float32), self._check("done", done, (self.num_envs,), t.uint8)
+        pr, pd = self._arg("raw_reward", raw_reward, (self.num_envs,)), self._arg("done", done, (self.num_envs,), self.torch.uint8)
         self._stream()
         _lib.check(self.lib.qs_ars_account(self.h, pr, pd))
 
@@ -179,15 +138,15 @@ class DeviceARS:
         delta = self.delta if delta is None else delta
         if delta is None:
             raise RuntimeError("DeviceARS.finish before perturb")
-        p = self._check("delta", delta, (self.n_delta, self.n_params), self.torch.float32)
+        p = self._arg("delta", delta, (self.n_delta, self.n_params))
         self._stream()
-        _lib.check(self.lib.qs_ars_finish(self.h, C.c_void_p(self.theta.data_ptr()), p, self.n_top, self.learning_rate, self.alive_bonus_offset))
+        _lib.check(self.lib.qs_ars_finish(self.h, ptr(self.theta), p, self.n_top, self.learning_rate, self.alive_bonus_offset))
 
     # ---- sb3_contrib's surface
     def _step(self, actions, active=None):
-        """-> (obs, raw reward, done): DevicePPO._step's rule for the raw reward"""
+        """-> (obs, raw reward, done)"""
         obs, rew, done, _ = self.env.step_tensor(actions) if active is None else self.env.step_tensor(actions, active=active)
-        return obs, (self.env.old_reward if self._normalised else rew), done
+        return obs, raw_reward_of(self.env, rew), done
 
     def rollout(self):
         """One episode batch of every candidate (the candidates must be in place: perturb): -> the per-candidate returns [2 n_delta].  Stops
@@ -256,14 +215,3 @@ class DeviceARS:
                 at += o
         assert at == self.n_params
         return sd
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.qs_ars_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass

@@ -12,7 +12,7 @@ unspecified on the device), and a score that is not finite counts as -inf (a rob
 import ctypes as C
 
 from . import lib as _lib
-from .ars import _takes_active
+from .handle import DeviceHandle, env_mask, ptr, raw_reward_of, takes_active
 
 MAX_CANDIDATES = 4096      # csrc/qs_mpc.h: a robot's weights lie in one workgroup's LDS
 MAX_ELEMENTS = 1024        # horizon * action_dim: one lane per element of a sequence
@@ -20,10 +20,11 @@ METHOD = dict(best=0, mppi=1)                                                   
 GET = dict(plan=0, seq=1, score=2, running=3, best=4, best_score=5)                # QS_MPC_GET_*
 
 
-class DeviceMPC:
+class DeviceMPC(DeviceHandle):
     """The planner over a QuadrupedVecEnv, or a DeviceVecNormalize(training=False) around one (the scores then use old_reward, the raw
     reward, as DeviceARS does).  env may be None for a planner that is only handed rewards and dones (sample / feed / finish); it then needs
     action_dim and device."""
+    _prefix, _owner = "qs_mpc", "planner"
 
     def __init__(self, env, n_robots, n_candidates, horizon, sigma=0.5, method="best", temperature=1.0, freeze_done=False, seed=0,
                  action_dim=None, device=None):
@@ -57,7 +58,7 @@ class DeviceMPC:
                 raise ValueError(f"the environment has num_envs = {env.num_envs}, expected n_robots * (1 + n_candidates) = {self.num_envs}")
             if hasattr(env, "venv") and getattr(env, "training", False):
                 raise ValueError("DeviceMPC takes a DeviceVecNormalize with training=False (the candidates' rollouts must not move the statistics)")
-            if self.freeze_done and not _takes_active(env):
+            if self.freeze_done and not takes_active(env):
                 raise ValueError(f"freeze_done=True needs an environment whose step_tensor takes active= ({type(env).__name__}.step_tensor does not)")
             self.d, self.device = int(env.action_dim), env.device
         else:
@@ -83,35 +84,13 @@ class DeviceMPC:
         self.real_mask[:M] = 1
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(int(seed))
-        self._normalised = env is not None and hasattr(env, "venv") and hasattr(env, "old_reward")
         self._keep = None
         self._hold = None
-
-    # ---- plumbing
-    def _stream(self):
-        _lib.check(self.lib.qs_mpc_set_stream(self.h, C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
-
-    def _check(self, name, x, shape, dtype):
-        t = self.torch
-        if not t.is_tensor(x):
-            raise ValueError(f"{name} must be a torch tensor, got {type(x).__name__}")
-        if x.dtype != dtype:
-            raise ValueError(f"{name} must be {dtype}, got {x.dtype}")
-        if x.device != self.device:
-            raise ValueError(f"{name} is on {x.device}, this planner on {self.device}")
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {tuple(shape)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        return C.c_void_p(x.data_ptr())
 
     def get(self, what):
         """a device tensor with the handle's `what` (one of GET; a reused buffer, a stream-ordered copy): plan [M, H, d]; seq [H, M C, d];
         score float32 and running uint8 [M C]; best int32 and best_score float32 [M] of the last finish"""
-        out = self._out[what]
-        self._stream()
-        _lib.check(self.lib.qs_mpc_get(self.h, GET[what], C.c_void_p(out.data_ptr())))
-        return out
+        return self._get(what, GET, self._out)
 
     # ---- the steps of a control step (csrc/qs_mpc.h 1-3)
     def sample_eps(self):
@@ -120,7 +99,7 @@ class DeviceMPC:
 
     def sample(self, eps):
         """the candidates' sequences from eps [H, M C, d]: candidate 0 is the plan, the others clamp(plan + sigma * eps, -1, 1)"""
-        p = self._check("eps", eps, (self.H, self.M * self.C, self.d), self.torch.float32)
+        p = self._arg("eps", eps, (self.H, self.M * self.C, self.d))
         self._stream()
         _lib.check(self.lib.qs_mpc_sample(self.h, p, self.sigma))
         self._hold = eps
@@ -136,48 +115,38 @@ class DeviceMPC:
         pr = pd = pe = None
         stride = 0
         if h >= 1:
-            pr, pd = self._check("reward", reward, (n,), t.float32), self._check("done", done, (n,), t.uint8)
+            pr, pd = self._arg("reward", reward, (n,)), self._arg("done", done, (n,), t.uint8)
         if h == self.H:
             if not t.is_tensor(reward_end) or reward_end.dim() != 2:
                 raise ValueError("reward_end must be a float32 tensor [N, k] (get_info('reward_end'))")
-            pe, stride = self._check("reward_end", reward_end, (n, reward_end.shape[1]), t.float32), int(reward_end.shape[1])
+            pe, stride = self._arg("reward_end", reward_end, (n, reward_end.shape[1])), int(reward_end.shape[1])
         self._stream()
-        _lib.check(self.lib.qs_mpc_feed(self.h, h, pr, pd, pe, stride, C.c_void_p(self.actions.data_ptr()),
-                                        C.c_void_p(self.active.data_ptr()) if self.freeze_done else None))
+        _lib.check(self.lib.qs_mpc_feed(self.h, h, pr, pd, pe, stride, ptr(self.actions), ptr(self.active) if self.freeze_done else None))
         self._hold = (reward, done, reward_end)
 
     def finish(self):
         """the choice: self.actions[:M] = the chosen sequences' first actions, the plan = the rest with the last action held"""
         self._stream()
-        _lib.check(self.lib.qs_mpc_finish(self.h, METHOD[self.method], self.temperature, C.c_void_p(self.actions.data_ptr())))
+        _lib.check(self.lib.qs_mpc_finish(self.h, METHOD[self.method], self.temperature, ptr(self.actions)))
 
     def set_plan(self, plan):
-        p = self._check("plan", plan, (self.M, self.H, self.d), self.torch.float32)
+        p = self._arg("plan", plan, (self.M, self.H, self.d))
         self._stream()
         _lib.check(self.lib.qs_mpc_set_plan(self.h, p, None))
         self._hold = plan
 
     def reset_plan(self, indices=None):
         """zero plans for the robots `indices` (None: all): robot ids, or a bool / uint8 mask [M] on the device (used as it is, no wait)"""
-        t = self.torch
-        m = None
-        if indices is not None:
-            if t.is_tensor(indices) and indices.dtype in (t.bool, t.uint8):
-                if tuple(indices.shape) != (self.M,) or indices.device != self.device:
-                    raise ValueError(f"a mask must have shape {(self.M,)} on {self.device}")
-                m = indices.contiguous().view(t.uint8) if indices.dtype == t.bool else indices.contiguous()
-            else:
-                idx = t.as_tensor(indices, device=self.device).to(t.int64).reshape(-1)
-                m = t.zeros(self.M, dtype=t.uint8, device=self.device).index_fill_(0, idx, 1)
+        m = env_mask(indices, self.M, self.device)
         self._stream()
-        _lib.check(self.lib.qs_mpc_set_plan(self.h, None, None if m is None else C.c_void_p(m.data_ptr())))
+        _lib.check(self.lib.qs_mpc_set_plan(self.h, None, ptr(m)))
         self._hold = m
 
     # ---- the control loop
     def _step(self, active=None):
         """-> (raw reward, done) of one step of every environment under self.actions"""
         _, rew, done, _ = self.env.step_tensor(self.actions) if active is None else self.env.step_tensor(self.actions, active=active)
-        return (self.env.old_reward if self._normalised else rew), done
+        return raw_reward_of(self.env, rew), done
 
     def plan(self):
         """One control step's planning: fork, sample, H feeds and steps, finish.  Leaves the chosen first actions in self.actions[:M], the
@@ -210,14 +179,3 @@ class DeviceMPC:
         M = self.M
         self.reset_plan(done[:M])
         return obs[:M], rew[:M], done[:M], trunc[:M]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.qs_mpc_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass

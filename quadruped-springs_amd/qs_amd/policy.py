@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
+from .handle import DeviceHandle, ptr, tensor_arg
 
 ACTIVATIONS = {"none": 0, "tanh": 1, "relu": 2}
 MAX_HIDDEN = 4
@@ -127,7 +128,9 @@ def state_dict_from_zip(path):
         return torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu")
 
 
-class DevicePolicy:
+class DevicePolicy(DeviceHandle):
+    _prefix, _owner = "qs_policy", "policy"
+
     def __init__(self, obs_dim, action_dim, net_arch=(64, 64), activation="tanh", squash_output=False, bias=True, num_envs=1, n_policies=1,
                  clip=(-1.0, 1.0), device=0):
         import torch
@@ -166,7 +169,7 @@ class DevicePolicy:
         if tuple(p.shape) != (self.n_policies, self.n_params):
             raise ValueError(f"params has shape {tuple(params.shape)}, expected ({self.n_policies}, {self.n_params}) or ({self.n_params},)")
         p = p.to(device=self.device, dtype=t.float32).contiguous()
-        _lib.check(self.lib.qs_policy_set_params(self.h, C.c_void_p(p.data_ptr())))
+        _lib.check(self.lib.qs_policy_set_params(self.h, ptr(p)))
         self._params = p
 
     def get_params(self):
@@ -179,19 +182,8 @@ class DevicePolicy:
         self.log_std.copy_(self.torch.as_tensor(_to_numpy(log_std), dtype=self.torch.float32).reshape(self.action_dim))
 
     # ---- inference
-    def _check(self, name, x, shape):
-        t = self.torch
-        if not t.is_tensor(x):
-            raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
-        if x.dtype != t.float32:
-            raise TypeError(f"{name} must be float32, got {x.dtype}")
-        if x.device != self.device:
-            raise ValueError(f"{name} is on {x.device}, this policy on {self.device}")
-        if tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {tuple(shape)}")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        return C.c_void_p(x.data_ptr())
+    def _arg(self, name, x, shape):
+        return tensor_arg(name, x, shape, self.torch.float32, self.device, self._owner, kind_error=TypeError)
 
     def act(self, obs, eps=None, log_std=None, want_mean=False, want_log_prob=False):
         """-> actions [N, action_dim], clipped; with want_mean / want_log_prob a tuple (actions, mean, log_prob) with None for what was not
@@ -201,14 +193,13 @@ class DevicePolicy:
             raise RuntimeError("DevicePolicy.act before set_params")
         if want_log_prob and eps is None:
             raise ValueError("want_log_prob needs eps")
-        p_obs = self._check("obs", obs, (self.num_envs, self.obs_dim))
-        p_eps = None if eps is None else self._check("eps", eps, (self.num_envs, self.action_dim))
+        p_obs = self._arg("obs", obs, (self.num_envs, self.obs_dim))
+        p_eps = None if eps is None else self._arg("eps", eps, (self.num_envs, self.action_dim))
         ls = self.log_std if log_std is None else log_std
-        p_ls = None if eps is None else self._check("log_std", ls, (self.action_dim,))
-        _lib.check(self.lib.qs_policy_set_stream(self.h, C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
-        _lib.check(self.lib.qs_policy_act(self.h, p_obs, p_eps, p_ls, C.c_void_p(self._actions.data_ptr()),
-                                          C.c_void_p(self._mean.data_ptr()) if want_mean else None,
-                                          C.c_void_p(self._log_prob.data_ptr()) if want_log_prob else None))
+        p_ls = None if eps is None else self._arg("log_std", ls, (self.action_dim,))
+        self._stream()
+        _lib.check(self.lib.qs_policy_act(self.h, p_obs, p_eps, p_ls, ptr(self._actions), ptr(self._mean) if want_mean else None,
+                                          ptr(self._log_prob) if want_log_prob else None))
         if want_mean or want_log_prob:
             return self._actions, (self._mean if want_mean else None), (self._log_prob if want_log_prob else None)
         return self._actions
@@ -252,9 +243,7 @@ class DevicePolicy:
         return cls.from_state_dict(state_dict_from_zip(path), algo=algo, num_envs=num_envs, activation=activation, head=head, **kw)
 
     def close(self):
-        if self.h:
-            self.lib.qs_policy_destroy(self.h)
-            self.h = None
+        super().close()
         self._params = None
 
 

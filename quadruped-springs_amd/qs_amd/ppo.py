@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import lib as _lib
+from .handle import DeviceHandle, ptr, raw_reward_of
 from .policy import ACTIVATIONS, MAX_HIDDEN, _to_numpy, layer_shapes, layers_from_state_dict, param_count, state_dict_from_zip
 
 NO_CLIP = 3.0e38
@@ -40,9 +41,10 @@ def _sequential(flat, obs_dim, out_dim, arch, activation):
     return nn.Sequential(*mods)
 
 
-class DeviceActorCritic:
+class DeviceActorCritic(DeviceHandle):
     """SB3's ActorCriticPolicy (MlpPolicy) with separate trunks.  `device` an int (cuda:<int>) or anything torch.device takes; on a
     device that is not a GPU only the torch side exists (evaluate_actions, state_dict, the parameter views): collect / predict raise."""
+    _prefix, _owner = "qs_ac", "policy"
 
     def __init__(self, obs_dim, action_dim, net_arch=(64, 64), vf_arch=None, activation="tanh", num_envs=1, clip=(-1.0, 1.0), log_std_init=0.0,
                  ortho_init=True, device=0):
@@ -75,7 +77,7 @@ class DeviceActorCritic:
             self.h = C.c_void_p()
             _lib.check(self.lib.qs_ac_create(C.byref(desc(self.action_dim, net_arch, *self.clip)), C.byref(desc(1, vf_arch, -NO_CLIP, NO_CLIP)),
                                              self.device.index or 0, C.byref(self.h)))
-            _lib.check(self.lib.qs_ac_set_params(self.h, self._p(self.actor_params), self._p(self.critic_params)))
+            _lib.check(self.lib.qs_ac_set_params(self.h, ptr(self.actor_params), ptr(self.critic_params)))
             n, a = self.num_envs, self.action_dim
             self.env_actions = torch.zeros((n, a), **f32)          # the clipped actions of the last collect / predict
             self._scratch = None                                   # rows for predict / predict_values
@@ -96,10 +98,6 @@ class DeviceActorCritic:
                         lin.weight.uniform_(-r, r)
                         lin.bias.uniform_(-r, r)
 
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr())
-
     def parameters(self):
         """what an optimiser takes: the view-Parameters of both networks and log_std"""
         return list(self.actor.parameters()) + list(self.critic.parameters()) + [self.log_std]
@@ -109,26 +107,15 @@ class DeviceActorCritic:
         if self.h is None:
             raise RuntimeError(f"DeviceActorCritic.{what} runs on a GPU; this one was built on {self.device} (there is no CPU path)")
 
-    def _check(self, name, x, shape, dtype=None):
-        t = self.torch
-        dtype = dtype or t.float32
-        if not t.is_tensor(x) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}, got "
-                             f"{(x.dtype, tuple(x.shape), x.device) if t.is_tensor(x) else type(x).__name__}")
-        return C.c_void_p(x.data_ptr())
-
-    def _stream(self):
-        _lib.check(self.lib.qs_ac_set_stream(self.h, C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
-
     def collect(self, obs, eps, obs_row, action_row, value_row, log_prob_row):
         """One collected step in one launch: samples a = mean(obs) + exp(log_std) * eps, writes obs, the unclipped a, V(obs) and
         log_prob(a) into the given rows (row t of a rollout buffer) and returns the clipped actions for the environment (a reused buffer,
         valid until the next collect).  On torch's current stream."""
         self._need_device("collect")
         n, o, a = self.num_envs, self.obs_dim, self.action_dim
-        args = (self._check("obs", obs, (n, o)), self._check("eps", eps, (n, a)), self._p(self.log_std.data), self._p(self.env_actions),
-                self._check("obs_row", obs_row, (n, o)), self._check("action_row", action_row, (n, a)), self._check("value_row", value_row, (n,)),
-                self._check("log_prob_row", log_prob_row, (n,)))
+        args = (self._arg("obs", obs, (n, o)), self._arg("eps", eps, (n, a)), ptr(self.log_std.data), ptr(self.env_actions),
+                self._arg("obs_row", obs_row, (n, o)), self._arg("action_row", action_row, (n, a)), self._arg("value_row", value_row, (n,)),
+                self._arg("log_prob_row", log_prob_row, (n,)))
         self._stream()
         _lib.check(self.lib.qs_ac_collect(self.h, *args))
         return self.env_actions
@@ -139,8 +126,8 @@ class DeviceActorCritic:
         t = self.torch
         if out is None:
             out = t.zeros(self.num_envs, dtype=t.float32, device=self.device)
-        p_mask = None if mask is None else self._check("mask", mask, (self.num_envs,), t.uint8)
-        args = (self._check("obs", obs, (self.num_envs, self.obs_dim)), p_mask, self._check("out", out, (self.num_envs,)))
+        p_mask = None if mask is None else self._arg("mask", mask, (self.num_envs,), t.uint8)
+        args = (self._arg("obs", obs, (self.num_envs, self.obs_dim)), p_mask, self._arg("out", out, (self.num_envs,)))
         self._stream()
         _lib.check(self.lib.qs_ac_values(self.h, *args))
         return out
@@ -149,8 +136,8 @@ class DeviceActorCritic:
         """rewards[i] = fmaf(gamma, V(terminal_obs[i]), rewards[i]) where truncated[i], in place"""
         self._need_device("bootstrap")
         n = self.num_envs
-        args = (self._check("terminal_obs", terminal_obs, (n, self.obs_dim)), self._check("truncated", truncated, (n,), self.torch.uint8))
-        p_rew = self._check("rewards", rewards, (n,))
+        args = (self._arg("terminal_obs", terminal_obs, (n, self.obs_dim)), self._arg("truncated", truncated, (n,), self.torch.uint8))
+        p_rew = self._arg("rewards", rewards, (n,))
         self._stream()
         _lib.check(self.lib.qs_ac_bootstrap(self.h, *args, float(gamma), p_rew))
         return rewards
@@ -222,11 +209,6 @@ class DeviceActorCritic:
         """an SB3 model .zip: its `policy.pth` (stable_baselines3 is not imported)"""
         return cls.from_state_dict(state_dict_from_zip(path), num_envs=num_envs, activation=activation, **kw)
 
-    def close(self):
-        if self.h:
-            self.lib.qs_ac_destroy(self.h)
-            self.h = None
-
 
 class DeviceRolloutBuffer:
     """SB3's RolloutBuffer as [T, N, ...] float32 tensors on the device (episode_starts 0 / 1 as float32, as SB3 keeps them)."""
@@ -253,10 +235,10 @@ class DeviceRolloutBuffer:
         lv = last_values.to(device=self.device, dtype=t.float32).reshape(self.num_envs).contiguous()
         ld = dones.to(device=self.device).reshape(self.num_envs).contiguous()
         ld = ld.view(t.uint8) if ld.dtype == t.bool else ld.to(t.uint8)
-        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
         with t.cuda.device(self.device):
-            _lib.check(_lib.load().qs_gae(p(self.rewards), p(self.values), p(self.episode_starts), p(lv), p(ld), self.n_steps, self.num_envs, self.gamma,
-                                          self.gae_lambda, p(self.advantages), p(self.returns), C.c_void_p(t.cuda.current_stream(self.device).cuda_stream)))
+            _lib.check(_lib.load().qs_gae(ptr(self.rewards), ptr(self.values), ptr(self.episode_starts), ptr(lv), ptr(ld), self.n_steps, self.num_envs,
+                                          self.gamma, self.gae_lambda, ptr(self.advantages), ptr(self.returns),
+                                          C.c_void_p(t.cuda.current_stream(self.device).cuda_stream)))
         self._keep = (lv, ld)      # alive until the kernel has read them
 
     def get(self, batch_size=None, generator=None):
@@ -295,6 +277,14 @@ def ppo_loss(values, log_prob, entropy, old_values, old_log_prob, advantages, re
                       clip_fraction=clip_fraction)
 
 
+class _PpoUpdate(DeviceHandle):
+    """the qs_ppo handle of DevicePPO(update="device"), next to its policy's qs_ac handle"""
+    _prefix, _owner = "qs_ppo", "learner"
+
+    def __init__(self, learner):
+        self.lib, self.torch, self.device, self.h = _lib.load(), learner.torch, learner.device, C.c_void_p()
+
+
 class DevicePPO:
     """SB3's PPO over a QuadrupedVecEnv(auto_reset=True) or a DeviceVecNormalize around one.  env may be None for a learner that is only
     handed buffers (train())."""
@@ -330,13 +320,13 @@ class DevicePPO:
         self.generator.manual_seed(int(seed))
         self.num_timesteps = 0
         self._last_obs = None
-        self.hp = None
+        self._update = None           # the _PpoUpdate of update="device" on a GPU
         if update == "device":
             self._init_device_update(learning_rate)
         if env is not None:
             T, N = self.n_steps, policy.num_envs
             f32 = dict(dtype=torch.float32, device=self.device)
-            self._normalised = hasattr(env, "venv") and hasattr(env, "old_reward")
+            self._normalised = raw_reward_of(env, None) is not None      # (a DeviceVecNormalize: its step_tensor also takes terminal_obs=)
             self._last_done = torch.ones(N, dtype=torch.uint8, device=self.device)      # the first step of the first rollout starts an episode
             self._term = torch.zeros((N, policy.obs_dim), **f32)
             self._last_values = torch.zeros(N, **f32)
@@ -353,7 +343,7 @@ class DevicePPO:
             return obs, rew, done, trunc, env.old_reward
         obs, rew, done, trunc = env.step_tensor(actions)
         from .vec_env import INFO
-        _lib.check(env.lib.qs_get_info(env.h, INFO["terminal_obs"], C.c_void_p(self._term.data_ptr())))   # (on the stream step_tensor has just set)
+        _lib.check(env.lib.qs_get_info(env.h, INFO["terminal_obs"], ptr(self._term)))   # (on the stream step_tensor has just set)
         return obs, rew, done, trunc, rew
 
     def collect_rollouts(self):
@@ -425,15 +415,19 @@ class DevicePPO:
         self.adam_step = 0
         if self.device.type != "cuda":
             return
-        lib = self.lib = _lib.load()
+        up = self._update = _PpoUpdate(self)
+        self.lib = up.lib
 
         def desc(out_dim, arch):
             return _lib.QsPolicyDesc(pol.num_envs, 1, pol.obs_dim, out_dim, len(arch), (C.c_int32 * 4)(*arch), ACTIVATIONS[pol.activation], 0, 1, -NO_CLIP, NO_CLIP)
-        self.hp = C.c_void_p()
-        _lib.check(lib.qs_ppo_create(C.byref(desc(pol.action_dim, pol.net_arch)), C.byref(desc(1, pol.vf_arch)), self.n_steps * pol.num_envs,
-                                     self.device.index or 0, C.byref(self.hp)))
-        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
-        _lib.check(lib.qs_ppo_bind(self.hp, p(pol.actor_params), p(pol.critic_params), p(pol.log_std.data), p(self.exp_avg), p(self.exp_avg_sq)))
+        _lib.check(up.lib.qs_ppo_create(C.byref(desc(pol.action_dim, pol.net_arch)), C.byref(desc(1, pol.vf_arch)), self.n_steps * pol.num_envs,
+                                        self.device.index or 0, C.byref(up.h)))
+        _lib.check(up.lib.qs_ppo_bind(up.h, ptr(pol.actor_params), ptr(pol.critic_params), ptr(pol.log_std.data), ptr(self.exp_avg), ptr(self.exp_avg_sq)))
+
+    @property
+    def hp(self):
+        """the qs_ppo handle (None without one: update="torch", or no GPU)"""
+        return None if self._update is None else self._update.h
 
     def _read_stats(self):
         """the statistics of the last minibatch as python floats (waits for the device); raises if any minibatch since the last read
@@ -451,18 +445,16 @@ class DevicePPO:
         t, buf = self.torch, self.buffer
         if self.hp is None:
             raise RuntimeError(f'DevicePPO(update="device") trains on a GPU; this one was built on {self.device} (there is no CPU path)')
-        if idx.dtype != t.int64 or idx.device != self.device or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous int64 tensor on the learner's device")
-        p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        p_idx = self._update._arg("idx", idx, getattr(idx, "shape", ()), t.int64)      # (any shape: its numel() indices)
         self._hy = self._hyper()
-        _lib.check(self.lib.qs_ppo_set_stream(self.hp, C.c_void_p(t.cuda.current_stream(self.device).cuda_stream)))
-        _lib.check(self.lib.qs_ppo_grad(self.hp, p(buf.observations), p(buf.actions), p(buf.log_probs), p(buf.advantages), p(buf.returns),
-                                        buf.n_steps * buf.num_envs, p(idx), idx.numel(), C.byref(self._hy), p(self.grad), p(self._stats)))
+        self._update._stream()
+        _lib.check(self.lib.qs_ppo_grad(self.hp, ptr(buf.observations), ptr(buf.actions), ptr(buf.log_probs), ptr(buf.advantages), ptr(buf.returns),
+                                        buf.n_steps * buf.num_envs, p_idx, idx.numel(), C.byref(self._hy), ptr(self.grad), ptr(self._stats)))
 
     def adam_minibatch(self):
         """qs_ppo_adam with self.grad: clip_grad_norm_ and optimizer.step() in place on the policy's parameters"""
         self.adam_step += 1
-        _lib.check(self.lib.qs_ppo_adam(self.hp, C.c_void_p(self.grad.data_ptr()), C.byref(self._hy), self.adam_step, C.c_void_p(self._stats.data_ptr())))
+        _lib.check(self.lib.qs_ppo_adam(self.hp, ptr(self.grad), C.byref(self._hy), self.adam_step, ptr(self._stats)))
 
     def _train_device(self):
         t = self.torch
@@ -487,16 +479,9 @@ class DevicePPO:
         return out
 
     def close(self):
-        """frees the qs_ppo handle (also at garbage collection and at the end of a `with` block)"""
-        if getattr(self, "hp", None):
-            self.lib.qs_ppo_destroy(self.hp)
-            self.hp = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # (interpreter shutdown: the library may be gone already)
-            pass
+        """frees the qs_ppo handle (as its garbage collection does, and the end of a `with` block)"""
+        if self._update is not None:
+            self._update.close()
 
     def __enter__(self):
         return self

@@ -7,6 +7,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import lib as _lib
+from .handle import ptr as _ptr
 
 # utils/camera.py:14-20, 86-117: distance, yaw, pitch (degrees), vertical fov (degrees); target None = the base position (the camera follows
 # the robot), else a fixed world point
@@ -87,10 +88,6 @@ def rgb_view(rgba):
     """uint8 [m, H, W, 3] view of the packed RGBA buffer (R in the low byte)"""
     import torch
     return rgba.view(torch.uint8).view(*rgba.shape, 4)[..., :3]
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def render_states(states, params=None, camera="CLASSIC", width=DEFAULT_SIZE[0], height=DEFAULT_SIZE[1], depth=False, segmentation=False,

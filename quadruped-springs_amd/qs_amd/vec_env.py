@@ -10,6 +10,7 @@ import numpy as np
 
 from . import lib as _lib
 from .config import DEMO_FILES, OBSERVATION_EPS, build_config
+from .handle import DeviceHandle, active_mask, env_mask, ptr, to_device_nowait   # (active_mask: also imported from here by its users)
 from .render import DEFAULT_SIZE, as_camera, check_request, rgb_view, tile_images
 from .spaces import Box, SB3VecEnv
 
@@ -20,23 +21,9 @@ PARAM = dict(mu=0, spring_k=1, spring_b=2, kp=3, kd=4, all=5)
 FRAME = dict(link=1, world=2)   # QS_FRAME_LINK / QS_FRAME_WORLD = pybullet.LINK_FRAME / WORLD_FRAME
 
 
-def active_mask(active, num_envs, device):
-    """step_tensor's `active` as the contiguous uint8 [N] tensor the step kernel reads: a bool or uint8 tensor of shape [num_envs] on
-    `device`; anything else raises ValueError before any launch"""
-    import torch
-    if not torch.is_tensor(active):
-        raise ValueError(f"active must be a bool or uint8 torch tensor of shape {(num_envs,)} on {device}, got {type(active).__name__}")
-    if active.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"active must be a bool or uint8 tensor, got {active.dtype}")
-    if tuple(active.shape) != (num_envs,):
-        raise ValueError(f"active must have shape {(num_envs,)}, got {tuple(active.shape)}")
-    if active.device != torch.device(device):
-        raise ValueError(f"active is on {active.device}, the environments on {device}")
-    a = active.contiguous()
-    return a.view(torch.uint8) if a.dtype == torch.bool else a
+class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
+    _prefix, _owner = "qs", "environment"
 
-
-class QuadrupedVecEnv(SB3VecEnv):
     def __init__(self, num_envs=1, device=0, auto_reset=True, reset_lookahead=None, copy_outputs=True, solo_waves=None, solo_reach=None, **env_kwargs):
         """reset_lookahead = K: every environment keeps the settled reset states of its next K episodes ready (computed by extra workgroups
         of the step kernel while the environments step), so a reset is a copy; results are bitwise those of K = 0, where every reset runs
@@ -79,7 +66,6 @@ class QuadrupedVecEnv(SB3VecEnv):
         self.action_dim, self.obs_dim = d, self.cfg.obs_dim
         self._init_vec_env_base()
         self.h = C.c_void_p()
-        self._closed = False
         self._create(device)
         n, o = self.num_envs, self.obs_dim
         with torch.cuda.device(self.device):
@@ -128,14 +114,11 @@ class QuadrupedVecEnv(SB3VecEnv):
         reset hangs every robot again (on_rack=True handles only).  Never waits for the device."""
         if not self.on_rack:
             raise RuntimeError("set_rack needs a handle created with on_rack=True")
-        mask = None
-        if indices is not None:
-            m = np.zeros(self.num_envs, np.uint8)
-            m[np.asarray(self._indices(indices), np.int64)] = 1
-            mask = self.torch.from_numpy(m).pin_memory().to(self.device, non_blocking=True)
+        mask = env_mask(indices, self.num_envs, self.device)
+        if mask is not None:
             self._rack_keep = mask
         self._stream()
-        _lib.check(self.lib.qs_set_rack(self.h, None if mask is None else self._ptr(mask), 1 if hung else 0))
+        _lib.check(self.lib.qs_set_rack(self.h, ptr(mask), 1 if hung else 0))
 
     def _init_vec_env_base(self):
         """stable_baselines3.common.vec_env.VecEnv.__init__(num_envs, observation_space, action_space) when SB3 is importable and this
@@ -144,25 +127,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         if SB3VecEnv is not object:
             SB3VecEnv.__init__(self, self.num_envs, self.observation_space, self.action_space)
 
-    # ---- plumbing
-    def _stream(self):
-        s = self.torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self.lib.qs_set_stream(self.h, C.c_void_p(s)))
-
-    def _ptr(self, t):
-        return C.c_void_p(t.data_ptr())
-
-    def close(self):
-        if not getattr(self, "_closed", True) and self.h:
-            h, self.h = self.h, C.c_void_p()     # later calls reach the library with a null handle and fail with its error text
-            self.lib.qs_destroy(h)
-            self._closed = True
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+    _ptr = staticmethod(ptr)
 
     # ---- device-resident API
     def reset_tensor(self, mask=None, states=None):
@@ -174,9 +139,9 @@ class QuadrupedVecEnv(SB3VecEnv):
             m = self.torch.as_tensor(mask, device=self.device).to(self.torch.uint8).contiguous()
         if states is not None:
             st = self.torch.as_tensor(states, dtype=self.torch.float32, device=self.device).reshape(self.num_envs, 37).contiguous()
-            _lib.check(self.lib.qs_reset_to(self.h, None if m is None else self._ptr(m), self._ptr(st)))
+            _lib.check(self.lib.qs_reset_to(self.h, ptr(m), ptr(st)))
         else:
-            _lib.check(self.lib.qs_reset(self.h, None if m is None else self._ptr(m)))
+            _lib.check(self.lib.qs_reset(self.h, ptr(m)))
         _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
         return self._obs
 
@@ -206,12 +171,9 @@ class QuadrupedVecEnv(SB3VecEnv):
     def step_fused(self, actions, out):
         """One step with a single output: `out` [N, obs_dim + 2] float32 CUDA tensor = observation | reward | done + 2 * truncated
         (the row a sharded run all-gathers, qs_amd/sharded.py)."""
-        t = self.torch
-        for name, x, shape in (("actions", actions, (self.num_envs, self.action_dim)), ("out", out, (self.num_envs, self.obs_dim + 2))):
-            if tuple(x.shape) != shape or x.dtype != t.float32 or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        pa, po = self._arg("actions", actions, (self.num_envs, self.action_dim)), self._arg("out", out, (self.num_envs, self.obs_dim + 2))
         self._stream()
-        _lib.check(self.lib.qs_step_fused(self.h, self._ptr(actions), self._ptr(out)))
+        _lib.check(self.lib.qs_step_fused(self.h, pa, po))
         return out
 
     def get_state(self):
@@ -254,17 +216,6 @@ class QuadrupedVecEnv(SB3VecEnv):
         if frame not in FRAME:
             raise ValueError(f"frame must be one of {sorted(FRAME)}, got {frame!r}")
         n = self.num_envs
-        keep = []
-
-        def to_device(a):
-            """a host array onto the device without a synchronous copy: page-locked staging (the caching host allocator keeps the staging
-            block until the copy on the stream has read it), then an asynchronous copy"""
-            h = t.from_numpy(np.ascontiguousarray(a))
-            if self.device.type == "cpu":
-                return h
-            h = h.pin_memory()
-            keep.append(h)
-            return h.to(self.device, non_blocking=True)
 
         def rows(x, name):
             if isinstance(x, t.Tensor) and x.device == self.device:
@@ -277,7 +228,7 @@ class QuadrupedVecEnv(SB3VecEnv):
                     raise ValueError(f"{name} must have shape (3,) or {(n, 3)}, got {tuple(a.shape)}")
                 if not np.all(np.isfinite(a)):
                     raise ValueError(f"{name} must be finite")
-                v = to_device(a)
+                v = to_device_nowait(a, self.device)
             return v.expand(n, 3)
 
         self._stream()
@@ -300,21 +251,13 @@ class QuadrupedVecEnv(SB3VecEnv):
                 raise ValueError(f"substeps must be a scalar or have shape {(n,)}, got {tuple(a.shape)}")
             if np.any(a > 2 ** 31 - 1):
                 raise ValueError("substeps must fit an int32")
-            k = t.full((n,), int(a), dtype=t.int32, device=self.device) if a.shape == () else to_device(a.astype(np.int32))
+            k = t.full((n,), int(a), dtype=t.int32, device=self.device) if a.shape == () else to_device_nowait(a.astype(np.int32), self.device)
         k = k.contiguous()
-        m = None
-        if indices is not None:
-            if isinstance(indices, t.Tensor) and indices.device == self.device:
-                # (index_fill_ takes the value as a kernel argument; `m[idx] = 1` stages a host scalar and synchronises)
-                m = t.zeros(n, dtype=t.uint8, device=self.device).index_fill_(0, indices.to(t.int64), 1)
-            else:
-                mh = np.zeros(n, np.uint8)
-                mh[np.asarray(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices), np.int64)] = 1
-                m = to_device(mh)
-        _lib.check(self.lib.qs_set_external_wrench(self.h, None if m is None else self._ptr(m), self._ptr(w), self._ptr(k), FRAME[frame]))
+        m = env_mask(indices, n, self.device)
+        _lib.check(self.lib.qs_set_external_wrench(self.h, ptr(m), ptr(w), ptr(k), FRAME[frame]))
         # (everything here is ordered on the current stream; the references keep the device buffers from going back to the caching
         # allocator before the kernel has read them, the staging blocks are held by the host allocator until their copies are done)
-        self._push_keep = (w, k, m, keep)
+        self._push_keep = (w, k, m)
 
     # ---- snapshots and forks (include/qs_amd.h qs_snapshot / qs_restore / qs_fork)
     def snapshot_info(self):
@@ -323,24 +266,6 @@ class QuadrupedVecEnv(SB3VecEnv):
         info = SnapshotInfo()
         _lib.check(self.lib.qs_snapshot_info(self.h, C.byref(info)))
         return info.as_dict()
-
-    def _mask_of(self, indices):
-        """device uint8 [N] with ones at `indices` (None: no mask = all); host indices are checked here and go over without blocking"""
-        if indices is None:
-            return None
-        t = self.torch
-        if isinstance(indices, t.Tensor) and indices.device == self.device:
-            if indices.dtype == t.bool or indices.dtype == t.uint8:
-                if tuple(indices.shape) != (self.num_envs,):
-                    raise ValueError(f"a mask must have shape {(self.num_envs,)}, got {tuple(indices.shape)}")
-                return indices.to(t.uint8).contiguous()
-            return t.zeros(self.num_envs, dtype=t.uint8, device=self.device).index_fill_(0, indices.to(t.int64), 1)
-        idx = np.asarray(self._indices(indices.tolist() if isinstance(indices, (np.ndarray, t.Tensor)) else indices), np.int64)
-        if idx.size and (idx.min() < 0 or idx.max() >= self.num_envs):
-            raise ValueError(f"environment ids must lie in [0, {self.num_envs}), got {idx.min()} .. {idx.max()}")
-        m = np.zeros(self.num_envs, np.uint8)
-        m[idx] = 1
-        return t.from_numpy(m).pin_memory().to(self.device, non_blocking=True)
 
     def snapshot(self, indices=None, out=None):
         """The environments `indices` (None = all) as an EnvSnapshot: one row per environment with everything a step reads (the record, the
@@ -354,13 +279,11 @@ class QuadrupedVecEnv(SB3VecEnv):
             snap = EnvSnapshot(rows, info)
         else:
             check_fits(out.info, info, strict=True)
-            rows = out.rows
-            if rows.device != self.device or rows.dtype != t.float32 or not rows.is_contiguous() or tuple(rows.shape) != (info["n_envs"], info["row_floats"]):
-                raise ValueError(f"out.rows must be a contiguous float32 tensor of shape {(info['n_envs'], info['row_floats'])} on {self.device}")
-            snap = out
-        m = self._mask_of(indices)
+            rows, snap = out.rows, out
+        p_rows = self._arg("out.rows", rows, (info["n_envs"], info["row_floats"]))
+        m = env_mask(indices, self.num_envs, self.device)
         self._stream()
-        _lib.check(self.lib.qs_snapshot(self.h, None if m is None else self._ptr(m), self._ptr(rows)))
+        _lib.check(self.lib.qs_snapshot(self.h, ptr(m), p_rows))
         self._snap_keep = m
         return snap
 
@@ -378,9 +301,9 @@ class QuadrupedVecEnv(SB3VecEnv):
             raise ValueError(f"snapshot rows must be float32 of shape {(snap.info['n_envs'], snap.info['row_floats'])}, got {rows.dtype} {tuple(rows.shape)}")
         if rows.device != self.device or not rows.is_contiguous():
             rows = rows.contiguous().to(self.device)
-        m = self._mask_of(indices)
+        m = env_mask(indices, self.num_envs, self.device)
         self._stream()
-        _lib.check(self.lib.qs_restore(self.h, None if m is None else self._ptr(m), self._ptr(rows)))
+        _lib.check(self.lib.qs_restore(self.h, ptr(m), ptr(rows)))
         _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
         self._snap_keep = (m, rows)
         if not self._dirty:
@@ -424,7 +347,7 @@ class QuadrupedVecEnv(SB3VecEnv):
                     raise ValueError(f"src_of must be {n} integers, got {a.dtype} {a.shape}")
                 if a.min() < -1 or a.max() >= n:
                     raise ValueError(f"sources must lie in [-1, {n}), got {a.min()} .. {a.max()}")
-                so = t.from_numpy(a.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+                so = to_device_nowait(a.astype(np.int32), self.device)
             else:
                 if src_of.dtype.is_floating_point or src_of.dtype == t.bool or tuple(src_of.shape) != (n,):
                     raise ValueError(f"src_of must be an integer tensor of shape {(n,)}, got {src_of.dtype} {tuple(src_of.shape)}")
@@ -453,7 +376,7 @@ class QuadrupedVecEnv(SB3VecEnv):
                 raise ValueError("dst names an environment twice")
             a = np.full(n, -1, np.int32)
             a[d] = s.astype(np.int32) if s.size > 1 else np.int32(s[0])
-            so = t.from_numpy(a).pin_memory().to(self.device, non_blocking=True)
+            so = to_device_nowait(a, self.device)
         self._stream()
         _lib.check(self.lib.qs_fork(self.h, self._ptr(so)))
         _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
@@ -544,7 +467,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         v = t.as_tensor(values, device=self.device).to(t.int32).expand(self.num_envs).contiguous()
         m = None if mask is None else t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
         self._stream()
-        _lib.check(self.lib.qs_set_demo_counter(self.h, None if m is None else self._ptr(m), self._ptr(v)))
+        _lib.check(self.lib.qs_set_demo_counter(self.h, ptr(m), ptr(v)))
 
     def demo_counter(self):
         return self.get_info("task")[:, 44].to(self.torch.int64)
@@ -695,9 +618,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         seed = int(seed)
         if seed < 0:
             raise ValueError(f"seed must be a non-negative integer, got {seed}")
-        h, self.h = self.h, C.c_void_p()
-        if h:
-            self.lib.qs_destroy(h)
+        self.close()
         self.cfg.seed = seed
         self._views, self._dirty = {}, []
         self._infos = [{} for _ in range(self.num_envs)]
@@ -736,8 +657,7 @@ class QuadrupedVecEnv(SB3VecEnv):
             raise ValueError(f"indices must be integers, got {indices!r}")
         if a.size and (a.min() < 0 or a.max() >= self.num_envs):
             raise ValueError(f"environment ids must lie in [0, {self.num_envs}), got {a.min()} .. {a.max()}")
-        h = t.from_numpy(a.astype(np.int32)).pin_memory()
-        return h.to(self.device, non_blocking=True)
+        return to_device_nowait(a.astype(np.int32), self.device)
 
     def _render(self, indices, camera, width, height, depth, segmentation):
         t = self.torch
@@ -752,8 +672,7 @@ class QuadrupedVecEnv(SB3VecEnv):
         d = t.empty((m, height, width), dtype=t.float32, device=self.device) if depth else None
         sg = t.empty((m, height, width), dtype=t.int32, device=self.device) if segmentation else None
         c = cam.to_c()
-        _lib.check(self.lib.qs_render(self.h, self._ptr(ids), m, C.byref(c), width, height, self._ptr(rgba),
-                                      None if d is None else self._ptr(d), None if sg is None else self._ptr(sg)))
+        _lib.check(self.lib.qs_render(self.h, self._ptr(ids), m, C.byref(c), width, height, ptr(rgba), ptr(d), ptr(sg)))
         self._render_keep = ids
         return rgba, d, sg
 

@@ -10,9 +10,12 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
+from .handle import DeviceHandle, active_mask, env_mask, ptr
 
 
-class DeviceVecNormalize:
+class DeviceVecNormalize(DeviceHandle):
+    _prefix, _owner = "qs_norm", "wrapper"
+
     def __init__(self, venv, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8):
         self.venv = venv
         self.torch = venv.torch
@@ -28,19 +31,12 @@ class DeviceVecNormalize:
         self.old_reward = t.zeros(self.num_envs, dtype=t.float32, device=self.device)
         self._term = t.zeros((self.num_envs, self.obs_dim), dtype=t.float32, device=self.device)
 
-    def _stream(self):
-        _lib.check(self.lib.qs_norm_set_stream(self.h, C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)))
-
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr())
-
     # ---- device path
     def reset_tensor(self, mask=None):
         obs = self.venv.reset_tensor(mask)
         self.old_obs.copy_(obs)
         self._stream()
-        _lib.check(self.lib.qs_norm_reset(self.h, self._p(obs), int(self.training), int(self.norm_obs)))
+        _lib.check(self.lib.qs_norm_reset(self.h, ptr(obs), int(self.training), int(self.norm_obs)))
         return obs
 
     def step_tensor(self, actions, terminal_obs=None, active=None):
@@ -56,25 +52,20 @@ class DeviceVecNormalize:
             obs, rew, done, trunc = self.venv.step_tensor(actions)
             m = None
         else:
-            from .vec_env import active_mask
             m = active_mask(active, self.num_envs, self.device)
             obs, rew, done, trunc = self.venv.step_tensor(actions, active=m)
         p_term = None
         if terminal_obs is not None:
-            t = self.torch
-            if (terminal_obs.dtype, terminal_obs.device, tuple(terminal_obs.shape)) != (t.float32, self.device, (self.num_envs, self.obs_dim)) or \
-                    not terminal_obs.is_contiguous():
-                raise ValueError(f"terminal_obs must be a contiguous float32 tensor of shape {(self.num_envs, self.obs_dim)} on {self.device}")
             from .vec_env import INFO
-            p_term = self._p(terminal_obs)
+            p_term = self._arg("terminal_obs", terminal_obs, (self.num_envs, self.obs_dim))
             _lib.check(self.lib.qs_get_info(self.venv.h, INFO["terminal_obs"], p_term))      # (on the stream venv.step_tensor has just set)
         self._stream()
         if m is None:
-            _lib.check(self.lib.qs_norm_step(self.h, self._p(obs), self._p(rew), self._p(done), p_term, int(self.training), int(self.norm_obs),
-                                             int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
+            _lib.check(self.lib.qs_norm_step(self.h, ptr(obs), ptr(rew), ptr(done), p_term, int(self.training), int(self.norm_obs),
+                                             int(self.norm_reward), ptr(self.old_obs), ptr(self.old_reward)))
         else:
-            _lib.check(self.lib.qs_norm_step_masked(self.h, self._p(obs), self._p(rew), self._p(done), self._p(m), p_term, int(self.training),
-                                                    int(self.norm_obs), int(self.norm_reward), self._p(self.old_obs), self._p(self.old_reward)))
+            _lib.check(self.lib.qs_norm_step_masked(self.h, ptr(obs), ptr(rew), ptr(done), ptr(m), p_term, int(self.training),
+                                                    int(self.norm_obs), int(self.norm_reward), ptr(self.old_obs), ptr(self.old_reward)))
         return obs, rew, done, trunc
 
     def normalize_obs(self, obs):
@@ -131,8 +122,8 @@ class DeviceVecNormalize:
         step's terminal observations -- normalised -- to page-locked host memory."""
         v = self.venv
         v._stream()
-        _lib.check(self.lib.qs_host_set_norm(v.h, self.h, int(self.training), int(self.norm_obs), int(self.norm_reward), self._p(self.old_obs),
-                                             self._p(self.old_reward)))
+        _lib.check(self.lib.qs_host_set_norm(v.h, self.h, int(self.training), int(self.norm_obs), int(self.norm_reward), ptr(self.old_obs),
+                                             ptr(self.old_reward)))
         v._terminal_hook = self.normalize_obs      # (only used when more episodes end in one step than the compact list holds)
         try:
             v.step_async(actions)
@@ -177,7 +168,7 @@ class DeviceVecNormalize:
     def _returns(self):
         r = self.torch.empty(self.num_envs, dtype=self.torch.float64, device=self.device)
         self._stream()
-        _lib.check(self.lib.qs_norm_get_returns(self.h, self._p(r)))
+        _lib.check(self.lib.qs_norm_get_returns(self.h, ptr(r)))
         return r
 
     def _set_returns(self, r):
@@ -185,7 +176,7 @@ class DeviceVecNormalize:
         if tuple(r.shape) != (self.num_envs,):
             raise ValueError(f"returns must have shape {(self.num_envs,)}, got {tuple(r.shape)}")
         self._stream()
-        _lib.check(self.lib.qs_norm_set_returns(self.h, self._p(r)))
+        _lib.check(self.lib.qs_norm_set_returns(self.h, ptr(r)))
         self._returns_keep = r
 
     def snapshot(self, indices=None, out=None):
@@ -214,7 +205,7 @@ class DeviceVecNormalize:
             self._set_returns(ret)
             self.old_obs.copy_(old_obs); self.old_reward.copy_(old_rew)
         else:
-            m = self.venv._mask_of(indices).bool()
+            m = env_mask(indices, self.num_envs, self.device).bool()
             self._set_returns(t.where(m, ret, self._returns()))
             self.old_obs.copy_(t.where(m[:, None], old_obs, self.old_obs)); self.old_reward.copy_(t.where(m, old_rew, self.old_reward))
         if self.norm_obs:   # the handle keeps raw observations: normalise the returned buffer as a step does, without touching the statistics
@@ -255,11 +246,14 @@ class DeviceVecNormalize:
         self.set_stats(sb3.obs_rms.mean, sb3.obs_rms.var, sb3.obs_rms.count, sb3.ret_rms.mean, sb3.ret_rms.var, sb3.ret_rms.count)
         return self
 
-    def close(self):
-        if self.h:
+    def _free(self):
+        """the statistics' handle alone, which is all __del__ frees: the wrapped environment may outlive its wrapper"""
+        if vars(self).get("h"):
             self._detach()          # (the environment's host path must not keep a pointer to the statistics that go away now)
-            self.lib.qs_norm_destroy(self.h)
-            self.h = None
+        DeviceHandle.close(self)
+
+    def close(self):
+        self._free()
         self.venv.close()
 
     def __getattr__(self, name):   # everything else is the wrapped environment's
