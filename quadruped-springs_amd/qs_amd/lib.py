@@ -12,23 +12,6 @@ LIB_PATH = os.environ.get("QS_LIB_PATH") or os.path.join(_HERE, "libqs_hip.so") 
 ABI_VERSION = 8   # the last QS_ABI_VERSION that changed a struct or an existing entry point: the Structures below are that version's layouts
 ABI_LIBRARY = 9   # QS_ABI_VERSION of include/qs_amd.h this file was written against, the number load() demands of the library (9 added entries only)
 
-EXPORTS = (
-    "qs_create", "qs_destroy", "qs_set_stream", "qs_reset", "qs_reset_to", "qs_get_obs", "qs_step", "qs_step_fused", "qs_get_state", "qs_set_state",
-    "qs_info_dim", "qs_get_info", "qs_set_params", "qs_stats", "qs_enable_timing", "qs_last_step_kernel_ms",
-    "qs_settle_lanes", "qs_solo_waves", "qs_host_step_begin", "qs_host_step_end", "qs_set_trace", "qs_counter", "qs_counters_async", "qs_set_demo", "qs_set_demo_counter", "qs_set_external_wrench", "qs_create_ex", "qs_set_rack", "qs_render", "qs_render_states", "qs_last_error", "qs_version", "qs_abi_version",
-    "qs_norm_create", "qs_norm_destroy", "qs_norm_dims", "qs_norm_set_stream", "qs_norm_set_stats", "qs_norm_get_stats", "qs_norm_reset", "qs_norm_step",
-    "qs_norm_step_io", "qs_host_set_norm",
-    "qs_policy_create", "qs_policy_destroy", "qs_policy_set_stream", "qs_policy_param_count", "qs_policy_set_params", "qs_policy_act",
-    "qs_ac_create", "qs_ac_destroy", "qs_ac_set_stream", "qs_ac_set_params", "qs_ac_collect", "qs_ac_values", "qs_ac_bootstrap", "qs_gae",
-    "qs_snapshot_info", "qs_snapshot", "qs_restore", "qs_fork", "qs_norm_get_returns", "qs_norm_set_returns",
-    "qs_ppo_create", "qs_ppo_destroy", "qs_ppo_set_stream", "qs_ppo_bind", "qs_ppo_grad", "qs_ppo_adam", "qs_ppo_refusals",
-    "qs_ars_create", "qs_ars_destroy", "qs_ars_set_stream", "qs_ars_perturb", "qs_ars_begin", "qs_ars_account", "qs_ars_alive", "qs_ars_returns",
-    "qs_ars_finish", "qs_ars_get",
-    "qs_step_masked", "qs_norm_step_masked",
-    "qs_mpc_create", "qs_mpc_destroy", "qs_mpc_set_stream", "qs_mpc_sample", "qs_mpc_feed", "qs_mpc_finish", "qs_mpc_get", "qs_mpc_set_plan",
-)
-
-
 
 class HostResult(C.Structure):
     """qs_host_result (include/qs_amd.h): where the results of a host-path step lie in the handle's page-locked host memory."""
@@ -69,7 +52,119 @@ class QsPpoHyper(C.Structure):
                 ("lr", C.c_double), ("beta_one", C.c_double), ("beta_two", C.c_double), ("adam_eps", C.c_double)]
 
 
+class SnapshotInfo(C.Structure):
+    """struct qs_snapshot_info (include/qs_amd.h): which handles a snapshot's rows fit (qs_amd/snapshot.py hands it on)."""
+    _fields_ = [("bytes", C.c_uint64), ("n_envs", C.c_int32), ("row_floats", C.c_int32), ("rec_floats", C.c_int32), ("push_floats", C.c_int32),
+                ("obs_dim", C.c_int32), ("layout_version", C.c_int32), ("layout_digest", C.c_uint64), ("config_digest", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# every struct with a body in include/qs_amd.h, by its C name (tests/test_abi_cpu.py holds field types, sizes and offsets to the header and a C compile of it)
+STRUCTS = {"qs_config": QsConfig, "qs_rack": QsRack, "qs_host_result": HostResult, "qs_norm_io": NormIO, "qs_camera": QsCamera,
+           "qs_policy_desc": QsPolicyDesc, "qs_ppo_hyper": QsPpoHyper, "qs_snapshot_info": SnapshotInfo}
+
 PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm", "refused", "loss")   # QS_PPO_STAT_*
+
+_P, _vp, _i32, _f32, _f64, _ll = C.POINTER, C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong
+_out, _u64p, _pd, _desc, _hyper = _P(_vp), _P(C.c_uint64), _P(_f64), _P(QsPolicyDesc), _P(QsPpoHyper)
+# The binding, stated once: (entry point, return type, argument types) for every prototype of include/qs_amd.h, in the header's order.  A new
+# entry point is its prototype there and its row here; tests/test_abi_cpu.py holds every row to the header, kind by kind.  Array arguments are
+# c_void_p (callers pass data pointers as plain integers); POINTER(...) is kept for what callers pass with byref().
+SIGNATURES = (
+    ("qs_create", _i32, (_P(QsConfig), _i32, _out)),
+    ("qs_create_ex", _i32, (_P(QsConfig), _P(QsRack), _i32, _out)),
+    ("qs_set_rack", _i32, (_vp, _vp, _i32)),
+    ("qs_destroy", None, (_vp,)),
+    ("qs_set_stream", _i32, (_vp, _vp)),
+    ("qs_reset", _i32, (_vp, _vp)),
+    ("qs_reset_to", _i32, (_vp, _vp, _vp)),
+    ("qs_get_obs", _i32, (_vp, _vp)),
+    ("qs_set_demo", _i32, (_vp, _vp, _i32)),
+    ("qs_set_demo_counter", _i32, (_vp, _vp, _vp)),
+    ("qs_step", _i32, (_vp,) * 6),
+    ("qs_get_state", _i32, (_vp, _vp)),
+    ("qs_set_external_wrench", _i32, (_vp, _vp, _vp, _vp, _i32)),
+    ("qs_set_state", _i32, (_vp, _vp)),
+    ("qs_info_dim", _i32, (_vp, _i32)),
+    ("qs_get_info", _i32, (_vp, _i32, _vp)),
+    ("qs_set_params", _i32, (_vp, _i32, _vp)),
+    ("qs_stats", _i32, (_vp, _u64p, _u64p)),
+    ("qs_step_fused", _i32, (_vp, _vp, _vp)),
+    ("qs_step_masked", _i32, (_vp,) * 7),
+    ("qs_host_step_begin", _i32, (_vp, _vp)),
+    ("qs_host_step_end", _i32, (_vp, _P(HostResult))),
+    ("qs_counter", _i32, (_vp, _i32, _u64p)),
+    ("qs_counters_async", _i32, (_vp, _vp)),
+    ("qs_enable_timing", _i32, (_vp, _i32)),
+    ("qs_last_step_kernel_ms", _i32, (_vp, _P(_f32))),
+    ("qs_settle_lanes", _i32, (_vp, _i32)),
+    ("qs_solo_waves", _i32, (_vp, _i32, _f32)),
+    ("qs_set_trace", _i32, (_vp, _i32, _vp)),
+    ("qs_norm_create", _i32, (_i32, _i32, _f64, _f64, _f64, _f64, _i32, _out)),
+    ("qs_norm_destroy", None, (_vp,)),
+    ("qs_norm_set_stream", _i32, (_vp, _vp)),
+    ("qs_norm_set_stats", _i32, (_vp, _vp, _vp, _f64, _f64, _f64, _f64)),
+    ("qs_norm_dims", _i32, (_vp, _P(_i32), _P(_i32), _P(_i32))),
+    ("qs_norm_get_stats", _i32, (_vp, _vp, _vp, _pd, _pd, _pd, _pd)),
+    ("qs_norm_reset", _i32, (_vp, _vp, _i32, _i32)),
+    ("qs_norm_step", _i32, (_vp,) * 5 + (_i32,) * 3 + (_vp,) * 2),
+    ("qs_norm_step_masked", _i32, (_vp,) * 6 + (_i32,) * 3 + (_vp,) * 2),
+    ("qs_norm_step_io", _i32, (_vp, _P(NormIO), _i32, _i32, _i32)),
+    ("qs_host_set_norm", _i32, (_vp, _vp, _i32, _i32, _i32, _vp, _vp)),
+    ("qs_render", _i32, (_vp, _vp, _i32, _P(QsCamera), _i32, _i32, _vp, _vp, _vp)),
+    ("qs_render_states", _i32, (_vp, _vp, _i32, _P(QsCamera), _i32, _i32, _vp, _vp, _vp, _vp)),
+    ("qs_policy_create", _i32, (_desc, _i32, _out)),
+    ("qs_policy_destroy", None, (_vp,)),
+    ("qs_policy_set_stream", _i32, (_vp, _vp)),
+    ("qs_policy_param_count", _i32, (_vp,)),
+    ("qs_policy_set_params", _i32, (_vp, _vp)),
+    ("qs_policy_act", _i32, (_vp,) * 7),
+    ("qs_ac_create", _i32, (_desc, _desc, _i32, _out)),
+    ("qs_ac_destroy", None, (_vp,)),
+    ("qs_ac_set_stream", _i32, (_vp, _vp)),
+    ("qs_ac_set_params", _i32, (_vp, _vp, _vp)),
+    ("qs_ac_collect", _i32, (_vp,) * 9),
+    ("qs_ac_values", _i32, (_vp,) * 4),
+    ("qs_ac_bootstrap", _i32, (_vp, _vp, _vp, _f32, _vp)),
+    ("qs_gae", _i32, (_vp,) * 5 + (_i32, _i32, _f32, _f32, _vp, _vp, _vp)),
+    ("qs_ppo_create", _i32, (_desc, _desc, _i32, _i32, _out)),
+    ("qs_ppo_destroy", None, (_vp,)),
+    ("qs_ppo_set_stream", _i32, (_vp, _vp)),
+    ("qs_ppo_bind", _i32, (_vp,) * 6),
+    ("qs_ppo_grad", _i32, (_vp,) * 6 + (_ll, _vp, _i32, _hyper, _vp, _vp)),
+    ("qs_ppo_adam", _i32, (_vp, _vp, _hyper, _i32, _vp)),
+    ("qs_ppo_refusals", _i32, (_vp, _u64p)),
+    ("qs_ars_create", _i32, (_i32,) * 5 + (_out,)),
+    ("qs_ars_destroy", None, (_vp,)),
+    ("qs_ars_set_stream", _i32, (_vp, _vp)),
+    ("qs_ars_perturb", _i32, (_vp, _vp, _vp, _f32, _vp)),
+    ("qs_ars_begin", _i32, (_vp,)),
+    ("qs_ars_account", _i32, (_vp, _vp, _vp)),
+    ("qs_ars_alive", _i32, (_vp, _P(_i32))),
+    ("qs_ars_returns", _i32, (_vp, _f32)),
+    ("qs_ars_finish", _i32, (_vp, _vp, _vp, _i32, _f32, _f32)),
+    ("qs_ars_get", _i32, (_vp, _i32, _vp)),
+    ("qs_mpc_create", _i32, (_i32,) * 5 + (_out,)),
+    ("qs_mpc_destroy", None, (_vp,)),
+    ("qs_mpc_set_stream", _i32, (_vp, _vp)),
+    ("qs_mpc_sample", _i32, (_vp, _vp, _f32)),
+    ("qs_mpc_feed", _i32, (_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp)),
+    ("qs_mpc_finish", _i32, (_vp, _i32, _f32, _vp)),
+    ("qs_mpc_get", _i32, (_vp, _i32, _vp)),
+    ("qs_mpc_set_plan", _i32, (_vp, _vp, _vp)),
+    ("qs_snapshot_info", _i32, (_vp, _P(SnapshotInfo))),
+    ("qs_snapshot", _i32, (_vp, _vp, _vp)),
+    ("qs_restore", _i32, (_vp, _vp, _vp)),
+    ("qs_fork", _i32, (_vp, _vp)),
+    ("qs_norm_get_returns", _i32, (_vp, _vp)),
+    ("qs_norm_set_returns", _i32, (_vp, _vp)),
+    ("qs_last_error", C.c_char_p, ()),
+    ("qs_version", C.c_char_p, ()),
+    ("qs_abi_version", _i32, ()),
+)
+EXPORTS = tuple(name for name, *_ in SIGNATURES)
 
 _lib = None
 
@@ -87,121 +182,22 @@ def load():
     # with two HSA runtimes and the second one sees no device (measured on the MI355X box, tools/diag_hip_runtime.py).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int
-    lib.qs_create.argtypes = [C.POINTER(QsConfig), i32, C.POINTER(vp)]
-    lib.qs_destroy.argtypes = [vp]
-    lib.qs_destroy.restype = None
-    lib.qs_set_stream.argtypes = [vp, vp]
-    lib.qs_reset.argtypes = [vp, vp]
-    lib.qs_reset_to.argtypes = [vp, vp, vp]
-    lib.qs_get_obs.argtypes = [vp, vp]
-    lib.qs_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.qs_step_fused.argtypes = [vp, vp, vp]
-    lib.qs_get_state.argtypes = [vp, vp]
-    lib.qs_set_state.argtypes = [vp, vp]
-    lib.qs_info_dim.argtypes = [vp, i32]
-    lib.qs_get_info.argtypes = [vp, i32, vp]
-    lib.qs_set_params.argtypes = [vp, i32, vp]
-    lib.qs_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.qs_enable_timing.argtypes = [vp, i32]
-    lib.qs_last_step_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.qs_settle_lanes.argtypes = [vp, C.c_int]
-    lib.qs_host_step_begin.argtypes = [vp, vp]
-    lib.qs_host_step_end.argtypes = [vp, C.POINTER(HostResult)]
-    lib.qs_set_trace.argtypes = [vp, C.c_int, vp]
-    lib.qs_set_demo.argtypes = [vp, vp, C.c_int]
-    lib.qs_set_demo_counter.argtypes = [vp, vp, vp]
-    if hasattr(lib, "qs_set_external_wrench"):   # (ABI 6; an older library under QS_ALLOW_ABI_MISMATCH lacks it)
-        lib.qs_set_external_wrench.argtypes = [vp, vp, vp, vp, i32]
-    if hasattr(lib, "qs_create_ex"):   # (ABI 8)
-        lib.qs_create_ex.argtypes = [C.POINTER(QsConfig), C.POINTER(QsRack), i32, C.POINTER(vp)]
-        lib.qs_set_rack.argtypes = [vp, vp, i32]
-    if hasattr(lib, "qs_render"):   # (ABI 7)
-        lib.qs_render.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp]
-        lib.qs_render_states.argtypes = [vp, vp, i32, C.POINTER(QsCamera), i32, i32, vp, vp, vp, vp]
-    if hasattr(lib, "qs_solo_waves"):   # (added under ABI 9; an older library under QS_LIB_PATH lacks it)
-        lib.qs_solo_waves.argtypes = [vp, i32, C.c_float]
-    if hasattr(lib, "qs_step_masked"):   # (added under ABI 9; an older library under QS_LIB_PATH lacks them)
-        lib.qs_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        lib.qs_norm_step_masked.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    lib.qs_counter.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
-    lib.qs_counters_async.argtypes = [vp, vp]
-    f32, f64, pd = C.c_float, C.c_double, C.POINTER(C.c_double)
-    lib.qs_norm_create.argtypes = [i32, i32, f64, f64, f64, f64, i32, C.POINTER(vp)]
-    lib.qs_norm_destroy.argtypes = [vp]
-    lib.qs_norm_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.qs_norm_destroy.restype = None
-    lib.qs_norm_set_stream.argtypes = [vp, vp]
-    lib.qs_norm_set_stats.argtypes = [vp, vp, vp, f64, f64, f64, f64]
-    lib.qs_norm_get_stats.argtypes = [vp, vp, vp, pd, pd, pd, pd]
-    lib.qs_norm_reset.argtypes = [vp, vp, i32, i32]
-    lib.qs_norm_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    lib.qs_norm_step_io.argtypes = [vp, C.POINTER(NormIO), i32, i32, i32]
-    lib.qs_host_set_norm.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    if hasattr(lib, "qs_policy_create"):   # (added under ABI 8; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
-        lib.qs_policy_create.argtypes = [C.POINTER(QsPolicyDesc), i32, C.POINTER(vp)]
-        lib.qs_policy_destroy.argtypes = [vp]
-        lib.qs_policy_destroy.restype = None
-        lib.qs_policy_set_stream.argtypes = [vp, vp]
-        lib.qs_policy_param_count.argtypes = [vp]
-        lib.qs_policy_set_params.argtypes = [vp, vp]
-        lib.qs_policy_act.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(lib, "qs_ac_create"):   # (ABI 9)
-        lib.qs_ac_create.argtypes = [C.POINTER(QsPolicyDesc), C.POINTER(QsPolicyDesc), i32, C.POINTER(vp)]
-        lib.qs_ac_destroy.argtypes = [vp]
-        lib.qs_ac_destroy.restype = None
-        lib.qs_ac_set_stream.argtypes = [vp, vp]
-        lib.qs_ac_set_params.argtypes = [vp, vp, vp]
-        lib.qs_ac_collect.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.qs_ac_values.argtypes = [vp, vp, vp, vp]
-        lib.qs_ac_bootstrap.argtypes = [vp, vp, vp, f32, vp]
-        lib.qs_gae.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp]
-    if hasattr(lib, "qs_snapshot_info"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
-        from .snapshot import SnapshotInfo
-        lib.qs_snapshot_info.argtypes = [vp, C.POINTER(SnapshotInfo)]
-        lib.qs_snapshot.argtypes = [vp, vp, vp]
-        lib.qs_restore.argtypes = [vp, vp, vp]
-        lib.qs_fork.argtypes = [vp, vp]
-        lib.qs_norm_get_returns.argtypes = [vp, vp]
-        lib.qs_norm_set_returns.argtypes = [vp, vp]
-    if hasattr(lib, "qs_ppo_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
-        lib.qs_ppo_create.argtypes = [C.POINTER(QsPolicyDesc), C.POINTER(QsPolicyDesc), i32, i32, C.POINTER(vp)]
-        lib.qs_ppo_destroy.argtypes = [vp]
-        lib.qs_ppo_destroy.restype = None
-        lib.qs_ppo_set_stream.argtypes = [vp, vp]
-        lib.qs_ppo_bind.argtypes = [vp, vp, vp, vp, vp, vp]
-        lib.qs_ppo_grad.argtypes = [vp, vp, vp, vp, vp, vp, C.c_longlong, vp, i32, C.POINTER(QsPpoHyper), vp, vp]
-        lib.qs_ppo_adam.argtypes = [vp, vp, C.POINTER(QsPpoHyper), i32, vp]
-        lib.qs_ppo_refusals.argtypes = [vp, C.POINTER(C.c_uint64)]
-    if hasattr(lib, "qs_ars_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
-        lib.qs_ars_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.qs_ars_destroy.argtypes = [vp]
-        lib.qs_ars_destroy.restype = None
-        lib.qs_ars_set_stream.argtypes = [vp, vp]
-        lib.qs_ars_perturb.argtypes = [vp, vp, vp, f32, vp]
-        lib.qs_ars_begin.argtypes = [vp]
-        lib.qs_ars_account.argtypes = [vp, vp, vp]
-        lib.qs_ars_alive.argtypes = [vp, C.POINTER(C.c_int)]
-        lib.qs_ars_returns.argtypes = [vp, f32]
-        lib.qs_ars_finish.argtypes = [vp, vp, vp, i32, f32, f32]
-        lib.qs_ars_get.argtypes = [vp, i32, vp]
-    if hasattr(lib, "qs_mpc_create"):   # (added under ABI 9; an older library under QS_ALLOW_ABI_MISMATCH lacks them)
-        lib.qs_mpc_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-        lib.qs_mpc_destroy.argtypes = [vp]
-        lib.qs_mpc_destroy.restype = None
-        lib.qs_mpc_set_stream.argtypes = [vp, vp]
-        lib.qs_mpc_sample.argtypes = [vp, vp, f32]
-        lib.qs_mpc_feed.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp]
-        lib.qs_mpc_finish.argtypes = [vp, i32, f32, vp]
-        lib.qs_mpc_get.argtypes = [vp, i32, vp]
-        lib.qs_mpc_set_plan.argtypes = [vp, vp, vp]
-    lib.qs_last_error.restype = C.c_char_p
-    lib.qs_version.restype = C.c_char_p
-    # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change)
-    if os.environ.get("QS_ALLOW_ABI_MISMATCH") != "1" and (not hasattr(lib, "qs_abi_version") or lib.qs_abi_version() != ABI_LIBRARY):
-        have = lib.qs_abi_version() if hasattr(lib, "qs_abi_version") else "none (a library of round 4 or earlier)"
-        raise RuntimeError(f"{LIB_PATH} speaks ABI {have}, this binding was written against ABI {ABI_LIBRARY} of include/qs_amd.h: rebuild it "
-                           "(python quadruped-springs_amd/build.py --force)")
+    missing = []
+    for name, restype, argtypes in SIGNATURES:
+        fn = getattr(lib, name, None)
+        if fn is None:
+            missing.append(name)
+        else:
+            fn.restype, fn.argtypes = restype, argtypes
+    # (QS_ALLOW_ABI_MISMATCH=1: the A/B tools that time an older round's library through QS_LIB_PATH on entry points that did not change;
+    # the entries such a library lacks stay unbound)
+    if os.environ.get("QS_ALLOW_ABI_MISMATCH") != "1":
+        have = lib.qs_abi_version() if "qs_abi_version" not in missing else "none (a library of round 4 or earlier)"
+        rebuild = "rebuild it (python quadruped-springs_amd/build.py --force)"
+        if have != ABI_LIBRARY:
+            raise RuntimeError(f"{LIB_PATH} speaks ABI {have}, this binding was written against ABI {ABI_LIBRARY} of include/qs_amd.h: {rebuild}")
+        if missing:
+            raise RuntimeError(f"{LIB_PATH} reports ABI {have} and does not export {', '.join(missing)}, which include/qs_amd.h declares: {rebuild}")
     _lib = lib
     return lib
 

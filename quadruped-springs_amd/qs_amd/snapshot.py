@@ -3,24 +3,16 @@ with the fields of qs_snapshot_info that say which handles the rows fit, and `ex
 
 save() / load() use one .npz: the rows (as their uint32 bit patterns: NaN payloads and negative zeros survive), one JSON header, and one
 entry per array of `extras`.  numpy only; load() lands on the CPU and QuadrupedVecEnv.restore moves the rows to the device."""
-import ctypes as C
 import json
 
 import numpy as np
+
+from .lib import SnapshotInfo  # noqa: F401  (the Structure lies with the other mirrors of the header; importable from here as before)
 
 INFO_FIELDS = ("bytes", "n_envs", "row_floats", "rec_floats", "push_floats", "obs_dim", "layout_version", "layout_digest", "config_digest")
 # the fields two snapshots / handles must share for rows to fit (in the order they are compared and named), then what makes a resume exact
 LAYOUT_FIELDS = ("n_envs", "row_floats", "rec_floats", "push_floats", "obs_dim", "layout_version", "layout_digest")
 FORMAT = 1
-
-
-class SnapshotInfo(C.Structure):
-    """struct qs_snapshot_info (include/qs_amd.h)"""
-    _fields_ = [("bytes", C.c_uint64), ("n_envs", C.c_int32), ("row_floats", C.c_int32), ("rec_floats", C.c_int32), ("push_floats", C.c_int32),
-                ("obs_dim", C.c_int32), ("layout_version", C.c_int32), ("layout_digest", C.c_uint64), ("config_digest", C.c_uint64)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k in INFO_FIELDS}
 
 
 def first_difference(have, want, strict=True):

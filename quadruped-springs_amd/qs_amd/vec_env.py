@@ -127,8 +127,6 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
         if SB3VecEnv is not object:
             SB3VecEnv.__init__(self, self.num_envs, self.observation_space, self.action_space)
 
-    _ptr = staticmethod(ptr)
-
     # ---- device-resident API
     def reset_tensor(self, mask=None, states=None):
         """reset() of the masked environments (all when mask is None).  With `states` ([N,37], layout of get_state) the robots are
@@ -142,7 +140,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
             _lib.check(self.lib.qs_reset_to(self.h, ptr(m), ptr(st)))
         else:
             _lib.check(self.lib.qs_reset(self.h, ptr(m)))
-        _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
+        _lib.check(self.lib.qs_get_obs(self.h, ptr(self._obs)))
         return self._obs
 
     def step_tensor(self, actions, active=None):
@@ -161,10 +159,9 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
         m = None if active is None else active_mask(active, self.num_envs, self.device)
         self._stream()
         if m is None:
-            _lib.check(self.lib.qs_step(self.h, self._ptr(a), self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done), self._ptr(self._trunc)))
+            _lib.check(self.lib.qs_step(self.h, ptr(a), ptr(self._obs), ptr(self._rew), ptr(self._done), ptr(self._trunc)))
         else:
-            _lib.check(self.lib.qs_step_masked(self.h, self._ptr(a), self._ptr(m), self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done),
-                                               self._ptr(self._trunc)))
+            _lib.check(self.lib.qs_step_masked(self.h, ptr(a), ptr(m), ptr(self._obs), ptr(self._rew), ptr(self._done), ptr(self._trunc)))
         self._active_keep = m
         return self._obs, self._rew, self._done, self._trunc
 
@@ -179,27 +176,27 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
     def get_state(self):
         out = self.torch.empty((self.num_envs, 37), dtype=self.torch.float32, device=self.device)
         self._stream()
-        _lib.check(self.lib.qs_get_state(self.h, self._ptr(out)))
+        _lib.check(self.lib.qs_get_state(self.h, ptr(out)))
         return out
 
     def set_state(self, state):
         s = self.torch.as_tensor(state, dtype=self.torch.float32, device=self.device).contiguous().reshape(self.num_envs, 37)
         self._stream()
-        _lib.check(self.lib.qs_set_state(self.h, self._ptr(s)))
+        _lib.check(self.lib.qs_set_state(self.h, ptr(s)))
 
     def get_info(self, which):
         k = INFO[which] if isinstance(which, str) else int(which)
         dim = self.lib.qs_info_dim(self.h, k)
         out = self.torch.empty((self.num_envs, dim), dtype=self.torch.float32, device=self.device)
         self._stream()
-        _lib.check(self.lib.qs_get_info(self.h, k, self._ptr(out)))
+        _lib.check(self.lib.qs_get_info(self.h, k, ptr(out)))
         return out
 
     def set_params(self, which, values):
         k = PARAM[which] if isinstance(which, str) else int(which)
         v = self.torch.as_tensor(values, dtype=self.torch.float32, device=self.device).contiguous()
         self._stream()
-        _lib.check(self.lib.qs_set_params(self.h, k, self._ptr(v)))
+        _lib.check(self.lib.qs_set_params(self.h, k, ptr(v)))
         self.torch.cuda.current_stream(self.device).synchronize()  # `v` may be a temporary
 
     def apply_external_force(self, force, torque=None, substeps=None, frame="world", indices=None):
@@ -262,8 +259,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
     # ---- snapshots and forks (include/qs_amd.h qs_snapshot / qs_restore / qs_fork)
     def snapshot_info(self):
         """the qs_snapshot_info fields of this handle as a dict: the row's size, and the digests that say which snapshots fit it"""
-        from .snapshot import SnapshotInfo
-        info = SnapshotInfo()
+        info = _lib.SnapshotInfo()
         _lib.check(self.lib.qs_snapshot_info(self.h, C.byref(info)))
         return info.as_dict()
 
@@ -304,7 +300,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
         m = env_mask(indices, self.num_envs, self.device)
         self._stream()
         _lib.check(self.lib.qs_restore(self.h, ptr(m), ptr(rows)))
-        _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
+        _lib.check(self.lib.qs_get_obs(self.h, ptr(self._obs)))
         self._snap_keep = (m, rows)
         if not self._dirty:
             pass                                   # (every filled entry is listed there: a device-only loop never looks at its indices on the host)
@@ -378,8 +374,8 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
             a[d] = s.astype(np.int32) if s.size > 1 else np.int32(s[0])
             so = to_device_nowait(a, self.device)
         self._stream()
-        _lib.check(self.lib.qs_fork(self.h, self._ptr(so)))
-        _lib.check(self.lib.qs_get_obs(self.h, self._ptr(self._obs)))
+        _lib.check(self.lib.qs_fork(self.h, ptr(so)))
+        _lib.check(self.lib.qs_get_obs(self.h, ptr(self._obs)))
         self._fork_keep = so
         return so
 
@@ -401,7 +397,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
         synchronisation: read it (.cpu()) whenever convenient."""
         out = self.torch.zeros(8, dtype=self.torch.int64, device=self.device)
         self._stream()
-        _lib.check(self.lib.qs_counters_async(self.h, self._ptr(out)))
+        _lib.check(self.lib.qs_counters_async(self.h, ptr(out)))
         return out
 
     def solo_waves(self, f=None, reach=None):
@@ -438,7 +434,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
             _lib.check(self.lib.qs_set_trace(self.h, -1, None))
             return
         self._trace = self.torch.zeros((self.cfg.action_repeat, 70), dtype=self.torch.float32, device=self.device)
-        _lib.check(self.lib.qs_set_trace(self.h, int(env), self._ptr(self._trace)))
+        _lib.check(self.lib.qs_set_trace(self.h, int(env), ptr(self._trace)))
 
     def get_trace(self, as_dict=True):
         """Rows [action_repeat, 70] of the traced environment for the most recent step; with as_dict the monitor_state.py
@@ -458,7 +454,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
             raise ValueError(f"demonstration rows have {self.action_dim + 38} entries, got shape {rows.shape}")
         t = self.torch.from_numpy(rows).to(self.device)
         self._stream()
-        _lib.check(self.lib.qs_set_demo(self.h, self._ptr(t), int(rows.shape[0])))   # synchronises: `t` may go
+        _lib.check(self.lib.qs_set_demo(self.h, ptr(t), int(rows.shape[0])))   # synchronises: `t` may go
         self.demo_list, self.demo_length = rows, int(rows.shape[0])
 
     def set_demo_counter(self, values, mask=None):
@@ -672,7 +668,7 @@ class QuadrupedVecEnv(DeviceHandle, SB3VecEnv):
         d = t.empty((m, height, width), dtype=t.float32, device=self.device) if depth else None
         sg = t.empty((m, height, width), dtype=t.int32, device=self.device) if segmentation else None
         c = cam.to_c()
-        _lib.check(self.lib.qs_render(self.h, self._ptr(ids), m, C.byref(c), width, height, ptr(rgba), ptr(d), ptr(sg)))
+        _lib.check(self.lib.qs_render(self.h, ptr(ids), m, C.byref(c), width, height, ptr(rgba), ptr(d), ptr(sg)))
         self._render_keep = ids
         return rgba, d, sg
 

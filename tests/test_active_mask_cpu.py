@@ -1,6 +1,5 @@
-"""step_tensor(active=) without a device: the entry points are declared and bound, the float64 restatement of the masked VecNormalize
+"""step_tensor(active=) without a device: where the mask stands in the two prototypes, the float64 restatement of the masked VecNormalize
 (tests/active_ref.py) is the unmasked one under a full mask, and the argument errors that are raised before anything is launched."""
-import ctypes as C
 import os
 import re
 
@@ -12,20 +11,9 @@ from active_ref import MaskedVecNormalizeRef
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_the_masked_entries_are_declared_and_bound():
-    from qs_amd import lib
+def test_the_mask_is_the_third_and_the_fifth_argument():
+    """of qs_step_masked and of qs_norm_step_masked, a const uint8_t* in both (every argument's kind against the binding: test_abi_cpu.py)"""
     header = open(os.path.join(REPO, "include", "qs_amd.h")).read()
-    vp, i32 = C.c_void_p, C.c_int32
-    l = lib.load()
-    # (C declaration -> ctypes argument list: every pointer a c_void_p, every int a c_int32)
-    for name, argtypes in (("qs_step_masked", [vp] * 7), ("qs_norm_step_masked", [vp] * 6 + [i32] * 3 + [vp] * 2)):
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert m, f"{name} is not declared in include/qs_amd.h"
-        args = [a.strip() for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
-        assert ["*" in a for a in args] == [t is vp for t in argtypes], (name, args)
-        assert name in lib.EXPORTS and hasattr(l, name), name
-        assert list(getattr(l, name).argtypes) == argtypes, name
-    # the mask is the third argument of the step and the fifth of the normalisation, a const uint8_t* in both
     bare = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
     assert "qs_step_masked(qs_handle* h, const float* actions, const uint8_t* active ," in bare
     assert "qs_norm_step_masked(qs_norm* h, float* obs , float* rew , const uint8_t* done , const uint8_t* active ," in bare

@@ -4,7 +4,6 @@ build bit for bit with a joint at its stop, the many-rows solve's rack rows agai
 release and a re-hang, the bindings' refusals, and the schedules of push_rack_cases.py -- hung under PD, hung on a low anchor with the
 feet on the floor, released and hung again while falling, joints at their stops -- against the float64 oracle under the yardstick, the
 rack's reaction included (the CPU twins of test_gpu_rack.py).  No GPU."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -12,7 +11,6 @@ from scipy.spatial.transform import Rotation
 
 from oracle.qso import Oracle
 from qs_amd.config import build_config
-from qs_amd import lib as qlib
 from emu.emu import Emu
 from emu.emu_rack import ANCHOR, rack_info, reset_rack, set_rack, step_rack
 from test_emu_hand_over import assert_bitwise
@@ -291,24 +289,6 @@ def test_on_rack_refusals():
     with pytest.raises(NotImplementedError, match="render") as ei:
         build_config(n_envs=1, render=True, on_rack=True)
     assert "on_rack" not in str(ei.value)
-
-
-def test_rack_struct_matches_the_header():
-    """qs_amd.lib.QsRack mirrors include/qs_amd.h's qs_rack field by field (offsets and size from a C compile of the header)"""
-    import os
-    import subprocess
-    import tempfile
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = ('#include <stddef.h>\n#include <stdio.h>\n#include "qs_amd.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(qs_rack), '
-           'offsetof(qs_rack, on), offsetof(qs_rack, anchor_pos), offsetof(qs_rack, anchor_quat)); return 0; }\n')
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "r.c")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I" + os.path.join(repo, "include"), "-o", os.path.join(d, "r"), c])
-        got = [int(x) for x in subprocess.check_output([os.path.join(d, "r")]).split()]
-    R = qlib.QsRack
-    assert got == [C.sizeof(R), R.on.offset, R.anchor_pos.offset, R.anchor_quat.offset]
-    assert qlib.ABI_VERSION == 8
 
 
 def test_gym_env_robot_reports_the_rack_position():

@@ -1,5 +1,5 @@
 """CPU-side checks of the product: the C-ABI library builds, loads and exports every symbol include/qs_amd.h declares
-(no compute calls without a GPU), the config struct matches the header, the host registries mirror the reference."""
+(no compute calls without a GPU), the host registries mirror the reference."""
 import ctypes as C
 import os
 import re
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from qs_amd import config as qcfg
-from qs_amd.config import QsConfig, build_config
+from qs_amd.config import build_config
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,6 +28,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(l, name), f"{name} declared in include/qs_amd.h but not exported"
     assert set(lib.EXPORTS) == declared
+    for name, restype, argtypes in lib.SIGNATURES:   # load() binds every row as the table states it (the table against the header: test_abi_cpu.py)
+        assert getattr(l, name).restype is restype and tuple(getattr(l, name).argtypes) == argtypes, name
 
 
 def test_the_library_says_which_sources_it_was_built_from():
@@ -40,51 +42,6 @@ def test_the_library_says_which_sources_it_was_built_from():
     spec.loader.exec_module(b)
     b.build()
     assert lib.source_sha() == b.source_fingerprint()
-
-
-def test_config_struct_layout_matches_header():
-    """Compile a tiny C program that prints sizeof/offsetof of qs_config and compare with the ctypes mirror."""
-    import subprocess
-    import tempfile
-    fields = [f[0] for f in QsConfig._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "qs_amd.h"\nint main(){printf("%zu\\n", sizeof(qs_config));\n'
-    for f in fields:
-        src += f'printf("%zu\\n", offsetof(qs_config, {f}));\n'
-    src += "return 0;}\n"
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), "-o", os.path.join(d, "t"), os.path.join(d, "t.c")])
-        out = subprocess.check_output([os.path.join(d, "t")]).decode().split()
-    assert int(out[0]) == C.sizeof(QsConfig)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(QsConfig, f).offset == int(off), f
-    # the oracle's qso_config has the same layout
-    src2 = src.replace("qs_amd.h", "qso.h").replace("qs_config", "qso_config")
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(src2)
-        subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "oracle"), "-o", os.path.join(d, "t"), os.path.join(d, "t.c")])
-        out2 = subprocess.check_output([os.path.join(d, "t")]).decode().split()
-    assert out2 == out
-
-
-def test_host_result_and_norm_io_layouts_match_header():
-    """The two other structs that cross the C ABI by pointer (qs_host_result, qs_norm_io) against their ctypes mirrors in qs_amd/lib.py."""
-    import subprocess
-    import tempfile
-    from qs_amd.lib import HostResult, NormIO
-    for cname, mirror in (("qs_host_result", HostResult), ("qs_norm_io", NormIO)):
-        fields = [f[0] for f in mirror._fields_]
-        src = '#include <stdio.h>\n#include <stddef.h>\n#include "qs_amd.h"\nint main(){printf("%zu\\n", sizeof(' + cname + '));\n'
-        for f in fields:
-            src += f'printf("%zu\\n", offsetof({cname}, {f}));\n'
-        src += "return 0;}\n"
-        with tempfile.TemporaryDirectory() as d:
-            open(os.path.join(d, "t.c"), "w").write(src)
-            subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), "-o", os.path.join(d, "t"), os.path.join(d, "t.c")])
-            out = subprocess.check_output([os.path.join(d, "t")]).decode().split()
-        assert int(out[0]) == C.sizeof(mirror), cname
-        for f, off in zip(fields, out[1:]):
-            assert getattr(mirror, f).offset == int(off), (cname, f)
 
 
 def test_no_gpu_means_loud_failure():

@@ -1,8 +1,7 @@
-"""The PPO update without a GPU: the C ABI's entries, DevicePPO(update="device") and what it refuses, the host twin of csrc/qs_ppo_train.h
+"""The PPO update without a GPU: the size of qs_ppo_hyper, DevicePPO(update="device") and what it refuses, the host twin of csrc/qs_ppo_train.h
 (tests/emu/qs_emu_ppo_train.cpp) under tests/ppo_train_ref.py's yardstick -- gradient, statistics, the part reduction and the sample order,
 the tie rule, clip and Adam -- and the stand-alone sanitizer driver."""
 import os
-import re
 import subprocess
 import sys
 
@@ -16,7 +15,6 @@ sys.path.insert(0, HERE)
 import ppo_train_ref as T  # noqa: E402
 from emu import emu_ppo_train as E  # noqa: E402
 
-ENTRIES = ("qs_ppo_create", "qs_ppo_destroy", "qs_ppo_set_stream", "qs_ppo_bind", "qs_ppo_grad", "qs_ppo_adam", "qs_ppo_refusals")
 NO_CLIP = (-3.0e38, 3.0e38)
 
 
@@ -33,18 +31,9 @@ def twin_grad(pol, data, idx, hyper):
 
 
 # ---- 1. the C ABI and the Python surface
-def test_the_update_entries_are_declared_bound_and_exported():
-    from qs_amd import lib
-    header = open(os.path.join(REPO, "include", "qs_amd.h")).read()
-    declared = set(re.findall(r"\b(qs_[a-z_]+)\s*\(", header))
-    l = lib.load()
-    for name in ENTRIES:
-        assert name in declared, f"{name} is not declared in include/qs_amd.h"
-        assert name in lib.EXPORTS, name
-        assert hasattr(l, name), f"{name} is not exported by {lib.LIB_PATH}"
-        assert getattr(l, name).argtypes is not None, name
-    assert lib.ABI_LIBRARY == 9 and l.qs_abi_version() == 9
+def test_the_hyper_struct_has_the_size_of_the_host_builds():
     import ctypes as C
+    from qs_amd import lib
     assert C.sizeof(lib.QsPpoHyper) == C.sizeof(E.Hyper) == 56 and len(lib.PPO_STATS) == 8
 
 

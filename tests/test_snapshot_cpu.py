@@ -1,4 +1,4 @@
-"""Device snapshots without a device: the six new entries are declared, bound and exported; EnvSnapshot files keep every bit; the digests
+"""Device snapshots without a device: INFO_FIELDS are qs_snapshot_info's; EnvSnapshot files keep every bit; the digests
 decide which snapshots an environment takes; and csrc/qs_snapshot.h -- the row's layout and the lane-level copies the kernels run -- moves
 every float exactly once on the host, under AddressSanitizer and UBSan (a stand-alone program: tests/sanitize/drv_snapshot.cpp)."""
 import os
@@ -9,35 +9,12 @@ import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = ("qs_snapshot_info", "qs_snapshot", "qs_restore", "qs_fork", "qs_norm_get_returns", "qs_norm_set_returns")
-
-
-def test_the_snapshot_entries_are_declared_bound_and_exported():
-    from qs_amd import lib
-    header = open(os.path.join(REPO, "include", "qs_amd.h")).read()
-    declared = set(re.findall(r"\b(qs_[a-z_]+)\s*\(", header))
-    l = lib.load()
-    for name in ENTRIES:
-        assert name in declared, f"{name} is not declared in include/qs_amd.h"
-        assert name in lib.EXPORTS, name
-        assert hasattr(l, name), f"{name} is not exported by {lib.LIB_PATH}"
-        assert getattr(l, name).argtypes is not None, f"{name} is not bound by qs_amd/lib.py"
-    assert l.qs_abi_version() == 9 and lib.ABI_LIBRARY == 9
 
 
 def test_the_info_struct_matches_the_header():
-    """struct qs_snapshot_info field by field against qs_amd/snapshot.py's ctypes Structure"""
-    import ctypes as C
+    """INFO_FIELDS, the keys of a snapshot's header, are qs_snapshot_info's fields in the struct's order (the Structure against the header: test_abi_cpu.py)"""
     from qs_amd.snapshot import INFO_FIELDS, SnapshotInfo
-    header = open(os.path.join(REPO, "include", "qs_amd.h")).read()
-    body = re.search(r"struct qs_snapshot_info \{(.*?)\n\};", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for typ, names in re.findall(r"(uint64_t|int32_t)\s+([a-z_, ]+);", body):
-        fields += [(n.strip(), typ) for n in names.split(",")]
-    assert [n for n, _ in fields] == list(INFO_FIELDS)
-    ctype = dict(uint64_t=C.c_uint64, int32_t=C.c_int32)
-    assert [(n, ctype[t]) for n, t in fields] == list(SnapshotInfo._fields_)
+    assert [n for n, _ in SnapshotInfo._fields_] == list(INFO_FIELDS) and list(SnapshotInfo().as_dict()) == list(INFO_FIELDS)
 
 
 def _info(**kw):

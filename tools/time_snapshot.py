@@ -25,6 +25,7 @@ def main():
     a = ap.parse_args()
     import torch
     from qs_amd import lib as _lib
+    from qs_amd.handle import ptr
     from qs_amd.vec_env import QuadrupedVecEnv
     kw = dict(task_env="JUMPING_IN_PLACE", observation_space_mode="PPO_BASIC", enable_springs=True, enable_action_filter=True,
               env_randomizer_mode="GROUND_RANDOMIZER", seed=1, noise=False, auto_reset=True)
@@ -48,7 +49,7 @@ def main():
         perm = torch.as_tensor(rng.permutation(n).astype(np.int32), device=v.device)
         v._stream()
         turn = itertools.count()
-        h, L, p = v.h, v.lib, v._ptr
+        h, L, p = v.h, v.lib, ptr
         cases = dict(snapshot=lambda: L.qs_snapshot(h, None, p(rows)), restore=lambda: L.qs_restore(h, None, p(rows)),
                      fork_one_to_all=lambda: L.qs_fork(h, p(one)), fork_permutation=lambda: L.qs_fork(h, p(perm)),
                      copy_same_bytes=lambda: twin.copy_(rows), step=lambda: w.step_tensor(acts[next(turn) % 16]))
