@@ -193,6 +193,32 @@ def rare_solve(cfg, rows, env, warm, pay=None):
     return lam12, plam
 
 
+_SO_SUBSTEP = os.path.join(_HERE, "libqs_emu_substep.so")
+SUBSTEP_BUILDS = {"full": 0, "hot": 1, "hot_soft": 2}
+_substep_lib = None
+
+
+def build_substep():
+    """one substep of every build tests/hip/substep_probe.hip holds (qs_emu_substep.cpp): a library of its own, on demand"""
+    return _compile(_SO_SUBSTEP, os.path.join(_HERE, "qs_emu_substep.cpp"))
+
+
+def substep(cfg, recs, tau, push=None, build="full"):
+    """the emulation twin of tests/hip/substep_probe.py's substep(): recs [n, QS_REC], tau [n, 12], push [n, 8] or None -> (records after
+    the substep, substep's return value [n]); each environment decides its own give-up"""
+    global _substep_lib
+    if _substep_lib is None:
+        _substep_lib = C.CDLL(build_substep())
+    out, tau = np.array(recs, np.float32, order="C"), np.ascontiguousarray(tau, np.float32)
+    n = out.shape[0]
+    push = None if push is None else np.ascontiguousarray(push, np.float32)
+    assert tau.shape == (n, 12) and (push is None or push.shape == (n, 8))
+    ret = np.full(n, -1, np.int32)
+    rc = _substep_lib.qse_substep(C.byref(cfg), n, SUBSTEP_BUILDS[build], _p(out), _p(tau), _p(push), _p(ret))
+    assert rc == 0, rc
+    return out, ret
+
+
 def build_stride(cfg, rack):
     """qs::Build::of(cfg, rack) as launch_step uses it: (rec_stride, step_lds_bytes), and the layout's QS_REC_END, QS_INFO_END"""
     out = [C.c_int() for _ in range(3)]

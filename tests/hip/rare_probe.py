@@ -20,8 +20,8 @@ CORES = {"default": 0, "0_4": 1, "0_6": 2, "18_12": 3}      # RareSolver::solve<
 ERR_SHAPE = -2                                              # a forced <0, 4> / <0, 6> refused a row set it cannot hold
 
 
-def _deps():
-    return [_SRC, _BUILD_PY, os.path.join(_REPO, "include", "qs_amd.h")] + \
+def _deps(src):
+    return [src, _BUILD_PY, os.path.join(_REPO, "include", "qs_amd.h")] + \
         sorted(glob.glob(os.path.join(_REPO, "quadruped-springs_amd", "csrc", "*.h")))
 
 
@@ -32,22 +32,27 @@ def _build_mod():
     return mod
 
 
-def build():
-    """hipcc --offload-arch=gfx950 with build.py's options into librare_probe.so next to this file, when a header, the probe or the options
+def build_probe(src, so):
+    """hipcc --offload-arch=gfx950 with build.py's options: the probe `src` into the library `so`, when a header, the probe or the options
     are newer (cross-compiles without a GPU)"""
-    if os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in _deps()):
-        return _SO
+    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in _deps(src)):
+        return so
     b = _build_mod()
-    tmp = "%s.%d.tmp" % (_SO, os.getpid())   # (renamed into place: a concurrent loader never sees half a library)
-    cmd = lambda form: [b.hipcc()] + b.hipcc_flags(form) + ["-I" + os.path.join(_REPO, "include"), "-o", tmp, _SRC]
+    tmp = "%s.%d.tmp" % (so, os.getpid())   # (renamed into place: a concurrent loader never sees half a library)
+    cmd = lambda form: [b.hipcc()] + b.hipcc_flags(form) + ["-I" + os.path.join(_REPO, "include"), "-o", tmp, src]
     r = subprocess.run(cmd(os.environ.get("QS_MFMA_VGPR_FORM", "1") != "0"), stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stderr)
         if "Rewrite AGPR-Copy-MFMA" not in r.stderr:   # (the back-end crash build.py also works round)
             raise subprocess.CalledProcessError(r.returncode, r.args)
         subprocess.check_call(cmd(False))
-    os.replace(tmp, _SO)
-    return _SO
+    os.replace(tmp, so)
+    return so
+
+
+def build():
+    """librare_probe.so next to this file"""
+    return build_probe(_SRC, _SO)
 
 
 _lib = None
